@@ -4,7 +4,12 @@
   python bench.py --gpus N --steps K --warmup W
   N > 1: one rank = one GPU = one federated client.  Either launched by `python -m torch.distributed.run --nproc-per-node N
   ... bench.py --gpus N ...` (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the environment), or started plainly, in which
-  case this script re-executes itself under torch.distributed.run with N ranks on 127.0.0.1.  WORLD_SIZE != N is an error.
+  case this script runs itself as a child job under torch.distributed.run with N ranks on 127.0.0.1.  WORLD_SIZE != N is an
+  error.
+  --dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step computed as DIR/<name>.npy (float32):
+  `loss.npy` = the three values train_step returns (loss_0, KL, L_0: the head of its buffer; the rest of that buffer is kernel
+  scratch, not output), `state.<key>.npy` = every trainable tensor it updated, under its state-dict key.
+  The inputs are seeded, so the same arguments give the same inputs on every run and two builds compare file for file.
 
 A "step" is one full reference train_step (task_trainer.py:280-330: P0 + P1 + P2, two AdamW/scheduler steps) on one
 batch of B=32 synthetic 384x384 image / 40-token question pairs per client (BASELINE.json configs[1]; configs[2] for
@@ -313,6 +318,34 @@ def make_exchange(eng, world, rank, dist):
     return (lambda: allreduce_average(eng, world)), desc
 
 
+def capture_step(eng, batch, use_graph):
+    """Capture the step graph ahead of the warm-up, so that the capture (which a graph-replayed train_step does on its first
+    call) is never inside the timed region, even at --warmup 0.  The engines save and restore the trainable state around a
+    capture, and the first step sets the same batch again: the steps compute exactly what they compute without this."""
+    if use_graph and eng.graph is None:
+        eng.set_batch(batch)
+        eng._capture()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, loss, state):
+    """--dump-outputs: the loss values train_step returned and the trainable tensors it updated in place (state-dict keys),
+    read back after the timed region, as DIR/<name>.npy in float32.  Both models' trainable state is far below the limit, so
+    every element is written."""
+    import numpy as np
+    arrays = {"loss": loss}
+    arrays.update({"state." + k: v for k, v in state.items()})
+    nbytes = sum(v.numel() * 4 for v in arrays.values())
+    if nbytes > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {nbytes} bytes, more than {DUMP_LIMIT_BYTES}")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name.replace(os.sep, "_") + ".npy"), t.detach().float().cpu().numpy())
+    return {"dir": out_dir, "arrays": len(arrays), "bytes": nbytes}
+
+
 def timed_round(step_fn, steps_r, warmup, exchange, dist, dev):
     """W warm-up steps (+ one exchange), barrier; then this rank's steps_r steps, [barrier], the exchange, barrier -- all
     inside the timed region.  Returns the round time (max over ranks is taken by the caller) and its split: this rank's
@@ -499,8 +532,11 @@ def bench_albef(args, world, rank, dev, dist):
     use_graph = not args.no_graph
     steps_r = hetero_steps(args.steps, rank) if args.hetero else args.steps
     exchange, coll = make_exchange(eng, world, rank, dist)
+    capture_step(eng, batches[0], use_graph)
     tr = timed_round(lambda i: eng.train_step(batches[i % 2], use_graph=use_graph), steps_r, args.warmup, exchange, dist, dev)
     dt, total_steps, rows = gather_ranks(tr, B, world, rank, dist, dev)
+    dumped = dump_outputs(args.dump_outputs, eng.acts["gating"]["loss"][:3], eng.state_dict()) \
+        if args.dump_outputs and rank == 0 else None
     loss = float(eng.acts["gating"]["loss"][0])
     if not (loss == loss):
         raise RuntimeError("non-finite loss")
@@ -532,6 +568,8 @@ def bench_albef(args, world, rank, dev, dist):
         out["mfma_frac_executed_flops"] = round(sps / world * exe_f / PEAK_BF16, 4)
         if rows is not None:
             out["per_rank"], out["round_split"] = rows, round_split(rows, dt, coll and coll.get("payload_bytes"))
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         if not args.no_roofline:
             try:
                 out["roofline"] = albef_roofline(L, eng, batches)
@@ -613,18 +651,24 @@ def main():
     ap.add_argument("--host-input", action="store_true",
                     help="also time the same steps with batches starting in pinned HOST memory (PCIe-inclusive rate, "
                          "uploads overlapped by feddat_amd.data.DevicePrefetcher); reported as extra fields")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's outputs (the loss values train_step returns and "
+                         "the trainable tensors it updated, rank 0) as DIR/<name>.npy in float32")
     args = ap.parse_args()
     args_fixup(args)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        # plain `python bench.py --gpus N`: become the N-rank job (one process per GPU, rendezvous on 127.0.0.1)
+        # plain `python bench.py --gpus N`: run the N-rank job (one process per GPU, rendezvous on 127.0.0.1) as a child
         import socket
+        import subprocess
         with socket.socket() as sk:
             sk.bind(("127.0.0.1", 0))
             port = sk.getsockname()[1]
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
                "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
-        os.execv(sys.executable, cmd)
+        sys.exit(subprocess.run(cmd).returncode)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world != args.gpus:
         raise SystemExit(f"bench.py: --gpus {args.gpus} but WORLD_SIZE={world}: launch with --nproc-per-node {args.gpus} "
@@ -668,8 +712,11 @@ def main():
     use_graph = not args.no_graph
     steps_r = hetero_steps(args.steps, rank) if args.hetero else args.steps
     exchange, coll = make_exchange(eng, world, rank, dist)
+    capture_step(eng, batches[0], use_graph)
     tr = timed_round(lambda i: eng.train_step(batches[i % nb], use_graph=use_graph), steps_r, args.warmup, exchange, dist, dev)
     dt, total_steps, rank_rows = gather_ranks(tr, B, world, rank, dist, dev)
+    # read back before anything below runs more steps on this engine (--host-input) or launches measurement kernels
+    dumped = dump_outputs(args.dump_outputs, eng.loss_buf["p2"][:3], eng.state_dict()) if args.dump_outputs and rank == 0 else None
     loss = float(eng.loss_buf["p2"][0])
     host_ms = None
     if args.host_input and world == 1:
@@ -763,6 +810,8 @@ def main():
             out["other_operand_format"] = other_fmt
         if rank_rows is not None:      # configs[2]: per-GPU rate and the round's split (compute / wait at the barrier / all-reduce)
             out["per_rank"], out["round_split"] = rank_rows, round_split(rank_rows, dt, coll and coll.get("payload_bytes"))
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         if not args.no_roofline:
             try:
                 out["roofline"] = roofline_block(L, eng, batches, gemms)

@@ -158,3 +158,33 @@ def test_bench_help_renders():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--help"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "--operands" in r.stdout, r.stderr[-500:]
+
+
+def test_bench_dump_outputs_writes_float32_arrays(tmp_path):
+    """--dump-outputs: the returned loss values and every trainable tensor, whole, one float32 .npy each, under the 64 MB cap."""
+    import numpy as np
+    import bench
+    loss = torch.tensor([1.5, 0.25, 2.0])
+    state = {"vilt.encoder.layer.0.output.adapter_1.down.weight": torch.randn(48, 768, dtype=torch.float64),
+             "heads.art.bias": torch.arange(100, dtype=torch.float32)}
+    info = bench.dump_outputs(str(tmp_path / "d"), loss, state)
+    assert info["arrays"] == 3 and info["bytes"] == 4 * (3 + 48 * 768 + 100)
+    got = np.load(tmp_path / "d" / "loss.npy")
+    assert got.dtype == np.float32 and got.tolist() == [1.5, 0.25, 2.0]
+    for k, v in state.items():
+        a = np.load(tmp_path / "d" / f"state.{k}.npy")
+        assert a.dtype == np.float32 and a.shape == tuple(v.shape) and np.array_equal(a, v.float().numpy())
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(tmp_path / "big"), loss, {"w": torch.zeros(bench.DUMP_LIMIT_BYTES // 4 + 1)})
+    assert not (tmp_path / "big").exists()
+
+
+def test_bench_rejects_zero_timed_steps():
+    """ms_per_step = the timed region / --steps: zero timed steps is an argument error, before any device work."""
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "0"], capture_output=True, text=True,
+                       timeout=300)
+    assert r.returncode == 2 and "--steps" in r.stderr, r.stderr[-500:]
