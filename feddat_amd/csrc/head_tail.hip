@@ -431,6 +431,40 @@ __global__ __launch_bounds__(1024) void dat_loss_single_kernel(const float* __re
     }
 }
 
+// Single-adapter step loss (optimizer_mode adapter; task_trainer.py:433-441): L = BCEWithLogits_mean(logits, target) * C and
+// dL/dlogits = (sigmoid(x) - t) / B in ONE launch.  Any C: lane j of a wave takes columns j, j + 64, ...; for C <= 128 a row's
+// terms are added in dat_loss_single_kernel's order and its batch sum is the same, so scalars[0] carries the same bits as
+// that kernel's BCE half.  Fixed-order reductions, no float atomics.
+__global__ __launch_bounds__(1024) void bce_loss_kernel(const float* __restrict__ logits, const float* __restrict__ target,
+                                                        int B, int C, float* __restrict__ dlogits,
+                                                        float* __restrict__ scalars, int* __restrict__ nonfinite) {
+    extern __shared__ float terms[];       // [B]
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const float inv_b = 1.0f / (float)B;
+    for (int b = wave; b < B; b += 16) {
+        float bce = 0.f;
+        for (int j = lane; j < C; j += 64) {
+            const float x = logits[(size_t)b * C + j];
+            const float y = target[(size_t)b * C + j];
+            bce += fmaxf(x, 0.f) - x * y + log1pf(expf(-fabsf(x)));
+            const float sig = 1.0f / (1.0f + expf(-x));
+            dlogits[(size_t)b * C + j] = (sig - y) * inv_b;
+        }
+        bce = wave_sum(bce);
+        if (lane == 0) terms[b] = bce;
+    }
+    __syncthreads();
+    if (wave != 0) return;
+    float bce = 0.f;
+    for (int b = lane; b < B; b += 64) bce += terms[b];
+    bce = wave_sum(bce);
+    if (lane == 0) {
+        const float l_bce = bce / (float)B;
+        scalars[0] = l_bce;
+        if (nonfinite && !(fabsf(l_bce) <= 3.4e38f)) atomicOr(nonfinite, 1);
+    }
+}
+
 __device__ __forceinline__ float ht_poly_lambda(int t, int warmup, int total) {     // = poly_lambda of loss_optim.hip
     if (t < warmup) return (float)t / (float)max(1, warmup);
     if (t > total) return 0.f;
@@ -551,6 +585,40 @@ __global__ void dat_step_finish_kernel(int* head_state, int* ad1_state, int* ad0
     scaler_i[0] = tracker;
     flags[0] = 0;
     flags[1] = 0;
+}
+
+// End of one single-adapter train_step under a dynamic loss scale: every counter moves by what was applied (one optimizer step
+// and one scheduler tick per batch), GradScaler.update() for one backward, flag cleared (include/feddat_hip.h).
+struct SingleFinish {
+    int* state[FEDDAT_ADAMW_MAX_GROUPS];
+    int n;
+};
+__global__ void single_step_finish_kernel(const SingleFinish s, int* flag, float* scaler_f, int* scaler_i, float growth,
+                                          float backoff, int growth_interval) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    const int applied = *flag ? 0 : 1;
+    for (int k = 0; k < s.n; ++k) {
+        s.state[k][0] += applied;
+        s.state[k][1] += applied;
+    }
+    float scale = scaler_f[0];
+    int tracker = scaler_i[0];
+    if (!applied) {
+        scale = fmaxf(scale * backoff, 6.103515625e-05f);
+        tracker = 0;
+        scaler_i[1] += 1;
+        scaler_i[2] += 1;
+    } else {
+        tracker += 1;
+        if (tracker >= growth_interval) {
+            scale = fminf(scale * growth, 1073741824.0f);
+            tracker = 0;
+        }
+    }
+    scaler_f[0] = scale;
+    scaler_f[1] = 1.0f / scale;
+    scaler_i[0] = tracker;
+    *flag = 0;
 }
 
 int ht_fill(HtJob& j, const feddat_ht_job& s) {
@@ -674,5 +742,28 @@ extern "C" int feddat_step_tick_multi(int* const* states, const int* d_sched, co
     }
     t.n = n;
     hipLaunchKernelGGL(step_tick_multi_kernel, dim3(1), dim3(64), 0, stream, t);
+    FD_LAUNCH_RET();
+}
+
+extern "C" int feddat_bce_loss_fwd_bwd(const float* logits, const float* target, int B, int C, float* dlogits, float* scalars,
+                                       int* nonfinite, hipStream_t stream) {
+    FD_CHECK_ARG(logits && target && dlogits && scalars && B > 0 && B <= 4096 && C > 0);
+    hipLaunchKernelGGL(bce_loss_kernel, dim3(1), dim3(1024), B * sizeof(float), stream, logits, target, B, C, dlogits, scalars,
+                       nonfinite);
+    FD_LAUNCH_RET();
+}
+
+extern "C" int feddat_single_step_finish(int* const* states, int n, int* flag, float* scaler_f, int* scaler_i, float growth,
+                                         float backoff, int growth_interval, hipStream_t stream) {
+    FD_CHECK_ARG(states && n >= 1 && n <= FEDDAT_ADAMW_MAX_GROUPS && flag && scaler_f && scaler_i && growth >= 1.0f &&
+                 backoff > 0.f && backoff <= 1.0f && growth_interval > 0);
+    SingleFinish s{};
+    for (int k = 0; k < n; ++k) {
+        FD_CHECK_ARG(states[k]);
+        s.state[k] = states[k];
+    }
+    s.n = n;
+    hipLaunchKernelGGL(single_step_finish_kernel, dim3(1), dim3(64), 0, stream, s, flag, scaler_f, scaler_i, growth, backoff,
+                       growth_interval);
     FD_LAUNCH_RET();
 }

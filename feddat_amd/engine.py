@@ -74,6 +74,11 @@ class FlatGroup:
 
 
 class ViltDatEngine:
+    # passes per sample through the backbone: the DAT step runs the gated and the adapter_1 pass as one batch of 2 B samples
+    NPASS = 2
+    # state-dict stems of the engine's adapters (adapter.py:22-58): slot a <-> "...output.adapter.<stem>{down,up}.{weight,bias}"
+    ADAPTER_STEMS = ("adapter_0_", "adapter_1_", "adapter_2_")
+
     def __init__(self, params: Dict[str, torch.Tensor], tasks: Sequence[str], device, batch: int, res: int,
                  text_len: int = 40, layers: int = 12, num_labels: int = 100, lr: float = 1e-4,
                  weight_decay: float = 1e-2, adam_eps: float = 1e-8, wgrad_splits: int = 16, fp8: bool = False,
@@ -222,10 +227,10 @@ class ViltDatEngine:
 
         # ---------------- trainable state: three adapters (flat per adapter) and one head per task ----------
         def adapter_names(a):
-            return [(ENC + f"encoder.layer.{i}.output.adapter.adapter_{a}_{t}",
+            return [(ENC + f"encoder.layer.{i}.output.adapter.{self.ADAPTER_STEMS[a]}{t}",
                      {"down.weight": (self.r, H), "down.bias": (self.r,), "up.weight": (H, self.r),
                       "up.bias": (H,)}[t]) for i in range(layers) for t in ADAPTER_TENSORS]
-        self.ad = [FlatGroup(adapter_names(a), dev, with_opt=(a != 2)) for a in range(3)]
+        self.ad = [FlatGroup(adapter_names(a), dev, with_opt=(a != 2)) for a in range(len(self.ADAPTER_STEMS))]
         self.ad_layer_numel = self.r * H + self.r + H * self.r + H
         head_shapes = {"clf_fc0.weight": (2 * H, H), "clf_fc0.bias": (2 * H,), "clf_norm0.weight": (2 * H,),
                        "clf_norm0.bias": (2 * H,), "clf_fc1.weight": (num_labels, 2 * H), "clf_fc1.bias": (num_labels,)}
@@ -236,12 +241,12 @@ class ViltDatEngine:
                 grp.view(n).copy_(params[n].to(dev, torch.float32))
         # bf16 operand copies of the adapters: [a][layer] -> dict(wd, wdT, wu, wuT, bd, bu)
         self._pack16 = {}
-        self.ad16 = [[self._alloc_pack(a, i) for i in range(layers)] for a in range(3)]
-        for a in range(3):
+        self.ad16 = [[self._alloc_pack(a, i) for i in range(layers)] for a in range(len(self.ad))]
+        for a in range(len(self.ad)):
             self.repack_adapter(a)
 
         # ---------------- workspace (static: a whole step is graph-capturable) ----------------
-        R, R2, B = self.R, 2 * self.R, batch
+        R, R2, B = self.R, self.NPASS * self.R, batch
 
         def f32(*s):
             return torch.empty(*s, device=dev)
@@ -257,7 +262,7 @@ class ViltDatEngine:
                         patch_mask=torch.ones(B, self.gh, self.gw, dtype=torch.int64, device=dev))
         # attention key masks of the [text | CLS | patches] sequence, derived on the device from the two HF masks
         # inside the step (no host sync, valid for every batch under one captured graph); rows [B, 2B) repeat [0, B)
-        self.key_mask2 = torch.ones(2 * B, self.S, dtype=torch.uint8, device=dev)
+        self.key_mask2 = torch.ones(self.NPASS * B, self.S, dtype=torch.uint8, device=dev)
         self.patches = b16(B * self.np, 3 * self.P * self.P)
         self.proj = f32(B * self.np, H)
         self.h0 = f32(R, H)
@@ -285,11 +290,11 @@ class ViltDatEngine:
         def u_buf():
             return torch.empty(R2, I, dtype=torch.uint8, device=dev) if self.g8u else b16(R2, I)
         self.act = [None] + [dict(h_in=f32(R2, H), st1=f32(R2, 2), qkv=b16(R2, 3 * H), ctx=b16(R2, H),
-                                  lse=f32(2 * B, self.heads, self.S), h2=f32(R2, H), st2=f32(R2, 2),
+                                  lse=f32(self.NPASS * B, self.heads, self.S), h2=f32(R2, H), st2=f32(R2, 2),
                                   u=u_buf(), h3=f32(R2, H)) for _ in range(1, layers)]
         self.h_out = f32(R2, H)        # output of the last adapter (dense path: single-layer models only)
         # top layer: only token 0 of each sample feeds the pooler, so everything after its attention runs on 2B rows
-        nb2 = 2 * B
+        nb2 = self.NPASS * B
         self.top = dict(h2=f32(nb2, H), st2=f32(nb2, 2), u=b16(nb2, I), h3=f32(nb2, H), x16=b16(nb2, H),
                         f16=b16(nb2, I), h_out=f32(nb2, H), dh3=f32(nb2, H), dh316=b16(nb2, H), dU=b16(nb2, I),
                         dx2=b16(nb2, H), dh2=f32(nb2, H), dh216=b16(nb2, H), dctx=f32(nb2, H))
@@ -363,7 +368,7 @@ class ViltDatEngine:
     # ------------------------------------------------------------------------------------------ adapters
     def _alloc_pack(self, a, i):
         H, r = self.H, self.r
-        base = ENC + f"encoder.layer.{i}.output.adapter.adapter_{a}_"
+        base = ENC + f"encoder.layer.{i}.output.adapter.{self.ADAPTER_STEMS[a]}"
         if a not in self._pack16:       # bf16 operand copies of all layers of adapter a: [layer][wd | wdT | wu | wuT]
             self._pack16[a] = torch.empty(self.nl, 4, r * H, dtype=self.op_dtype, device=self.dev)
         c = self._pack16[a][i]
@@ -468,10 +473,10 @@ class ViltDatEngine:
         if self.fused_tail:      # key mask + per-sample position grid + assembly in one launch (bit-identical)
             L.image_embed_assemble_masked(self.proj, self.cls, self.pos0, self.pos_grid, self.inp["patch_mask"],
                                           self.inp["attention_mask"], self.mod1, self.h0, self.key_mask2, B, Lt, self.gh,
-                                          self.gw, self.g0, H, nrep=2)
+                                          self.gw, self.g0, H, nrep=self.NPASS)
             return
         L.vilt_key_mask(self.inp["attention_mask"], self.inp["patch_mask"], self.key_mask2, B, Lt, self.gh, self.gw, 1,
-                        nrep=2)
+                        nrep=self.NPASS)
         L.pos_embed_resize_masked(self.pos_grid, self.inp["patch_mask"], self.pos_img, self.g0, B, self.gh, self.gw, 1,
                                   H)
         L.image_embed_assemble(self.proj, self.cls, self.pos0, self.pos_img, self.mod1, self.h0, B, Lt, self.np, S, H,
@@ -516,7 +521,8 @@ class ViltDatEngine:
     @_bound
     def _forward_dual(self):
         """Shared embeddings + layer-0 body, then both passes (gated | adapter_1) batched through layers 1..L-1."""
-        R, R2, B = self.R, 2 * self.R, self.B
+        R, R2, B = self.R, self.NPASS * self.R, self.B
+        nb = self.NPASS * B
         self._embed()
         l0 = self.l0
         m1 = self.key_mask2[:self.B]
@@ -540,19 +546,19 @@ class ViltDatEngine:
             # one C-ABI call per layer (feddat_vilt_layer_fwd): ViltLayer body + adapter + the next layer's layernorm_before
             if not self.use_layer_calls or self.fp8:
                 a = self.act[i]
-                self._layer_body(i, a["h_in"], R2, 2 * B, a["qkv"], a["ctx"], a["lse"], a["h2"], a["h3"], st1=a["st1"],
+                self._layer_body(i, a["h_in"], R2, nb, a["qkv"], a["ctx"], a["lse"], a["h2"], a["h3"], st1=a["st1"],
                                  st2=a["st2"], u=a["u"], mask=m2, ln1_done=True)
                 adapter_then_ln1(a["h3"], i, False)
                 continue
             Wn = self.layers[i + 1]
             W, A, _ = self._layer_struct(i)
-            L.vilt_layer_fwd(self.ctx, W, A, 2 * B, self.S, self.heads, self._segs(i, False, False), key_mask=m2,
+            L.vilt_layer_fwd(self.ctx, W, A, nb, self.S, self.heads, self._segs(i, False, False), key_mask=m2,
                              ln1_done=True, next_ln_g=Wn["ln1g"], next_ln_b=Wn["ln1b"])
         if self.nl > 1:
             self._top_layer_fwd(m2)
-            self._pool(self.top["h_out"], 2 * B, x_stride=self.H)
+            self._pool(self.top["h_out"], nb, x_stride=self.H)
         else:
-            self._pool(self.h_out, 2 * B)
+            self._pool(self.h_out, nb)
 
     def _sg(self, A, sa_i, sa_k, Bm, sb_k, sb_j, I, J, K, out, ksplit=1, bias_j=None, alpha=1.0):
         """Skinny exact-fp32 product; long contractions are split over the grid and reduced deterministically."""
@@ -581,7 +587,7 @@ class ViltDatEngine:
         strided GEMM operands."""
         i = self.nl - 1
         a, W, H, t = self.act[i], self.layers[i], self.H, self.top
-        R2, nb = 2 * self.R, 2 * self.B
+        R2, nb = self.NPASS * self.R, self.NPASS * self.B
         x16 = self.x16[:R2]       # LN1 of this layer: written by the previous layer's fused adapter + LN kernel
         if self._fp8_rows(R2):
             L.layernorm_fwd_fp8(a["h_in"], W["ln1g"], W["ln1b"], self.ln_eps, R2, H, self.x8[:R2], self.xs[:R2],
@@ -609,7 +615,7 @@ class ViltDatEngine:
     def _skinny_ws(self):
         """fp32 split-K partials of the top layer's 2B-row GEMMs (largest: 2B x 3072 x 768)."""
         if getattr(self, "_skws", None) is None:
-            nb, H, I = 2 * self.B, self.H, self.I
+            nb, H, I = self.NPASS * self.B, self.H, self.I
             n = max(L.gemm_skinny_workspace_elems(nb, I, H), L.gemm_skinny_workspace_elems(nb, H, I),
                     L.gemm_skinny_workspace_elems(nb, H, H), L.gemm_skinny_workspace_elems(nb, H, 3 * H)) if nb <= 64 else 0
             self._skws = torch.empty(max(n, 1), device=self.dev) if n else False
@@ -707,8 +713,8 @@ class ViltDatEngine:
     @_bound
     def _backward_dual(self):
         """dpooled [2B,H] -> adapter_0 grads (rows [0,R)) and adapter_1 grads (rows [R,2R))."""
-        R, R2, B, H = self.R, 2 * self.R, self.B, self.H
-        nb = 2 * B
+        R, R2, B, H = self.R, self.NPASS * self.R, self.B, self.H
+        nb = self.NPASS * B
         # the gradient entering the frozen backbone carries the loss scale from here on (alpha of this product; 1 for bf16
         # operands): every kernel below is linear in it, and feddat_wgrad_seg.grad_unscale takes it out again
         if self.fused_tail:      # d(pooler input) = (dpooled * (1 - pooled^2)) W_pool in one launch
@@ -787,18 +793,12 @@ class ViltDatEngine:
         FFN, LN2 and attention-output backward run on those rows; from the attention backward on every token is live."""
         i = self.nl - 1
         a, W, H, t = self.act[i], self.layers[i], self.H, self.top
-        R2, nb, B = 2 * self.R, 2 * self.B, self.B
+        R2, nb = self.NPASS * self.R, self.NPASS * self.B
         L.adapter_bwd(None, self.dcls, t["dh3"], self._top_segs(True), nb, dx_bf16=t["dh316"], z_out=self.z,
                       dz_out=self.dz, z_saved=self.zsave[i])
-        key = ("wg-top", self.opt_adapters)
-        if key not in self._segs_cache:
-            n = self.ad_layer_numel
-            segs = [dict(x=t["h3"][r0:], dy=self.dcls[r0:], z=self.z[r0:], dz=self.dz[r0:],
-                         grad=self.ad[ad].g[i * n:(i + 1) * n], rows=B, scale=sc, **self._scale_out())
-                    for ad, r0, sc in ((0, 0, 0.5), (1, B, 1.0)) if ad in self.opt_adapters]
-            self._segs_cache[key] = L.make_wgrad_segs(segs) if segs else None
-        if self._segs_cache[key] is not None:
-            L.adapter_wgrad_partial(self._segs_cache[key], self._wpart(i))
+        segs = self._top_wgrad_segs()
+        if segs is not None:
+            L.adapter_wgrad_partial(segs, self._wpart(i))
         ws = self._skinny_ws()
         L.gemm_bf16_nt(t["dh316"], W["w2T"], L.EPI_MUL_DGELU, aux=t["u"], out_bf16=t["dU"], skinny_workspace=ws)
         L.gemm_bf16_nt(t["dU"], W["w1T"], L.EPI_BF16, out_bf16=t["dx2"], skinny_workspace=ws)
@@ -823,11 +823,22 @@ class ViltDatEngine:
             L.gemm_bf16_nt(self.dqkv, W["wqkvT"], L.EPI_BF16, out_bf16=self.dx16)
         L.layernorm_bwd_dx(a["h_in"], a["st1"], W["ln1g"], R2, H, dy_bf16=self.dx16, dres=t["dh2"], dres_every=self.S, out_f32=oth)
 
+    def _top_wgrad_segs(self):
+        """Weight-gradient descriptor of the top layer's adapters (2B token-0 rows: adapter_0 | adapter_1)."""
+        key = ("wg-top", self.opt_adapters)
+        if key not in self._segs_cache:
+            i, t, B, n = self.nl - 1, self.top, self.B, self.ad_layer_numel
+            segs = [dict(x=t["h3"][r0:], dy=self.dcls[r0:], z=self.z[r0:], dz=self.dz[r0:],
+                         grad=self.ad[ad].g[i * n:(i + 1) * n], rows=B, scale=sc, **self._scale_out())
+                    for ad, r0, sc in ((0, 0, 0.5), (1, B, 1.0)) if ad in self.opt_adapters]
+            self._segs_cache[key] = L.make_wgrad_segs(segs) if segs else None
+        return self._segs_cache[key]
+
     def _layer_struct(self, i: int):
         """ctypes views of layer i's frozen weights and static activation buffers for the composite entry points."""
         if i not in self._layer_structs:
             Wd, a = self.layers[i], self.act[i]
-            R2 = 2 * self.R
+            R2 = self.NPASS * self.R
             W = L._fill(L.ViltLayerWeights, wqkv=Wd["wqkv"], wo=Wd["wo"], w1=Wd["w1"], w2=Wd["w2"], wqkvT=Wd["wqkvT"],
                         woT=Wd["woT"], w1T=Wd["w1T"], w2T=Wd["w2T"], bqkv=Wd["bqkv"], bo=Wd["bo"], b1=Wd["b1"], b2=Wd["b2"],
                         ln1_g=Wd["ln1g"], ln1_b=Wd["ln1b"], ln2_g=Wd["ln2g"], ln2_b=Wd["ln2b"])
@@ -1038,7 +1049,7 @@ class ViltDatEngine:
         """Capture the whole step into one hipGraph (all launches are on static buffers; the LR schedule and Adam
         step counts live on the device).  The optimizer state is saved/restored around the warm-up + capture
         run so that capturing does not advance training."""
-        groups = [self.ad[0], self.ad[1], self.head[self.task]]
+        groups = self._trained_groups()
         saved = [(g.p.clone(), g.m.clone(), g.v.clone(), g.state.clone()) for g in groups]
         saved_scaler = (self.scaler_f.clone(), self.scaler_i.clone(), self.ovf_flags.clone())
         s = torch.cuda.Stream()
@@ -1062,10 +1073,17 @@ class ViltDatEngine:
         self.scaler_f.copy_(saved_scaler[0])
         self.scaler_i.copy_(saved_scaler[1])
         self.ovf_flags.copy_(saved_scaler[2])
-        for a in (0, 1):
+        for a in self._trained_slots():
             self.repack_adapter(a)
         torch.cuda.synchronize()
         self.graph = graph
+
+    def _trained_groups(self) -> List[FlatGroup]:
+        """The groups a train_step updates (saved and restored around the capture)."""
+        return [self.ad[0], self.ad[1], self.head[self.task]]
+
+    def _trained_slots(self) -> Sequence[int]:
+        return (0, 1)
 
     def assert_finite(self):
         """Last line of defence.  With the dynamic loss scale (the default for fp16 operands) an overflowed sub-step is skipped

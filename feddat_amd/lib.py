@@ -142,6 +142,8 @@ _SIGS = {
     "feddat_dat_loss_fwd_bwd_single": [vp, vp, vp, i32, i32, f32, vp, vp, vp],
     "feddat_dat_loss_fwd_bwd_checked": [vp, vp, vp, i32, i32, f32, vp, vp, vp, vp],
     "feddat_dat_step_finish": [vp, vp, vp, vp, vp, vp, f32, f32, i32, vp],
+    "feddat_bce_loss_fwd_bwd": [vp, vp, i32, i32, vp, vp, vp, vp],
+    "feddat_single_step_finish": [C.POINTER(vp), i32, vp, vp, vp, f32, f32, i32, vp],
     "feddat_head_gemm": [C.POINTER(HtJob), i32, vp],
     "feddat_head_ln_gelu": [vp, vp, vp, f32, i32, i32, vp, vp, vp, vp],
     "feddat_head_ln_bwd_full": [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp],
@@ -735,6 +737,25 @@ def dat_step_finish(head_state, ad1_state, ad0_state, flags, scaler_f, scaler_i,
     _dev(head_state, ad1_state, ad0_state, flags, scaler_f, scaler_i)
     _chk(load().feddat_dat_step_finish(_p(head_state), _p(ad1_state), _p(ad0_state), _p(flags), _p(scaler_f), _p(scaler_i),
                                        growth, backoff, growth_interval, _stream()), "feddat_dat_step_finish")
+
+
+def bce_loss_fwd_bwd(logits, target, dlogits, scalars, nonfinite=None):
+    """scalars[0] = BCEWithLogits_mean(logits, target) * C, dlogits = (sigmoid(logits) - target) / B; nonfinite (int32 device
+    tensor, optional) gets 1 OR-ed in when the loss is inf / NaN (include/feddat_hip.h: feddat_bce_loss_fwd_bwd)."""
+    _dev(logits, target, dlogits, scalars)
+    B, Cn = logits.shape
+    assert scalars.numel() >= 1 and (nonfinite is None or nonfinite.dtype == torch.int32)
+    _chk(load().feddat_bce_loss_fwd_bwd(_p(logits), _p(target), B, Cn, _p(dlogits), _p(scalars),
+                                        _p(nonfinite), _stream()), "feddat_bce_loss_fwd_bwd")
+
+
+def single_step_finish(states, flag, scaler_f, scaler_i, growth=2.0, backoff=0.5, growth_interval=2000):
+    """End of a single-adapter train_step under the dynamic loss scale (include/feddat_hip.h: feddat_single_step_finish)."""
+    n = len(states)
+    _dev(*states, flag, scaler_f, scaler_i)
+    sp = (vp * n)(*[s.data_ptr() for s in states])
+    _chk(load().feddat_single_step_finish(sp, n, _p(flag), _p(scaler_f), _p(scaler_i), growth, backoff, growth_interval,
+                                          _stream()), "feddat_single_step_finish")
 
 
 def adamw_group(p, g, m, v, seg_off, seg_wd, state, d_sched=0, d_adam=0, skip_if=(), bak=None, bak_mode=0,

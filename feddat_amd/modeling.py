@@ -18,6 +18,7 @@ import torch
 
 from . import lib as L
 from .engine import ViltDatEngine, ENC
+from .modes import mode_names
 
 
 class _Param:
@@ -195,26 +196,43 @@ class ViltContinualLearner:
     BERT_LOCAL_PATH = "./models/bert-base-uncased"       # vilt.py:47
 
     def __init__(self, ordered_cl_tasks: List[str], params: Dict[str, torch.Tensor], device, batch_size: int,
-                 image_size: int = 384, num_layers: int = 12, lr: float = 1e-4, vocab=None, operands: str = None):
+                 image_size: int = 384, num_layers: int = 12, lr: float = 1e-4, vocab=None, operands: str = None,
+                 optimizer_mode: str = "dat"):
         """operands: 16-bit MFMA operand format of the engine, "f16" (default; the reference's mixed_precision: fp16,
-        accelerate_config.yaml:8) or "bf16" (engine.ViltDatEngine)."""
+        accelerate_config.yaml:8) or "bf16" (engine.ViltDatEngine).
+        optimizer_mode: "dat" (adapter_{0,1,2}, engine.ViltDatEngine) or "adapter" (the FedAvg baseline: one adapter per
+        layer, adapter_engine.ViltAdapterEngine; main.py:114-118,141-149)."""
         self.ordered_cl_tasks = list(ordered_cl_tasks)
         self.device = torch.device(device)
-        self.engine = ViltDatEngine(params, self.ordered_cl_tasks, self.device, batch=batch_size, res=image_size,
-                                    layers=num_layers, lr=lr, operands=operands)
+        self.optimizer_mode = optimizer_mode
+        if optimizer_mode == "adapter":
+            from .adapter_engine import ViltAdapterEngine
+            Engine = ViltAdapterEngine
+        elif optimizer_mode == "dat":
+            Engine = ViltDatEngine
+        else:
+            raise L.FeddatHipError(f"optimizer_mode must be 'dat' or 'adapter', got {optimizer_mode!r}")
+        self.engine = Engine(params, self.ordered_cl_tasks, self.device, batch=batch_size, res=image_size, layers=num_layers,
+                             lr=lr, operands=operands)
         self.max_text_length = self.engine.Lt               # vilt.py:50: config.max_position_embeddings = 40
         self._vocab = vocab
         self._tokenizer = None
         self._image_processor = None
         self.gating = False
-        self.active = "adapter_1"
+        self.active = "adapter_1" if optimizer_mode == "dat" else "adapter"
         # requires_grad flags per adapter, toggled exactly like adapter.py:66-95; prepare_model's initial state
-        # (main.py:157-159 + adapter.py:55-58): adapter_0/1 trainable, adapter_2 frozen
-        self.adapter_requires_grad = {0: True, 1: True, 2: False}
-        self.comm_state_dict_names = [n for n in self.state_dict() if "adapter_1" in n]   # main.py:160-163
+        # (main.py:157-159 + adapter.py:55-58): adapter_0/1 trainable, adapter_2 frozen.  The single adapter is always
+        # trainable (set_active_adapter('adapter') flips no flag)
+        self.adapter_requires_grad = {0: True, 1: True, 2: False} if optimizer_mode == "dat" else {0: True}
+        # main.py:141-149,160-163: adapter_1 (dat) / every adapter key (adapter)
+        self.comm_state_dict_names = mode_names(list(self.state_dict()), optimizer_mode)["communicated"]
 
     # ---- adapter switches (vilt.py:363-373) ----
     def set_active_adapter(self, name):
+        if self.optimizer_mode == "adapter":
+            if name != "adapter":
+                raise L.FeddatHipError(f"optimizer_mode adapter has one adapter, 'adapter' (got {name!r})")
+            return
         self.active = name
         if name == "adapter_0":
             self.adapter_requires_grad[0], self.adapter_requires_grad[1] = True, False
@@ -229,6 +247,8 @@ class ViltContinualLearner:
 
     def optimizer_adapters(self) -> Sequence[int]:
         """Which adapters a freshly created optimizer would hold (create_optimizer filters on requires_grad)."""
+        if self.optimizer_mode == "adapter":
+            return (0,)
         return tuple(a for a in (0, 1) if self.adapter_requires_grad[a])
 
     # ---- state dict with the reference's keys ----
@@ -243,7 +263,7 @@ class ViltContinualLearner:
         self.engine.load_tensors({k: v for k, v in sd.items() if k in own})
 
     def after_load(self):
-        for a in range(3):
+        for a in range(len(self.engine.ad)):
             self.engine.repack_adapter(a)
 
     # ---- the reference's batch schema (vilt.py:87-100): images + questions -> HF ViLT encodings, on the device ----
@@ -286,9 +306,11 @@ class ViltContinualLearner:
         return enc
 
     def forward(self, task_key: str, images, texts=None):
-        mode = "gating" if self.gating else self.active
         if not isinstance(images, dict):
             images = self.process_inputs(images, texts)
+        if self.optimizer_mode == "adapter":
+            return self.engine.forward(images, task_key)
+        mode = "gating" if self.gating else self.active
         return self.engine.forward(images, mode, task_key)
 
     __call__ = forward
@@ -296,11 +318,12 @@ class ViltContinualLearner:
 
 def create_vilt_continual_learner_model(params: Dict[str, torch.Tensor], ordered_cl_tasks: List[str], device,
                                         batch_size: int, image_size: int = 384, num_layers: int = 12,
-                                        lr: float = 1e-4, vocab=None, operands: str = None) -> ViltContinualLearner:
+                                        lr: float = 1e-4, vocab=None, operands: str = None,
+                                        optimizer_mode: str = "dat") -> ViltContinualLearner:
     """vilt.py:421-452 (the pretrained checkpoint is passed in as a tensor dict: feddat_amd.weights.load_vilt_pretrained
     reads it from a local HF directory; there is no hub access here)."""
     return ViltContinualLearner(ordered_cl_tasks, params, device, batch_size, image_size, num_layers, lr, vocab=vocab,
-                                operands=operands)
+                                operands=operands, optimizer_mode=optimizer_mode)
 
 
 def convert_batch_to_vilt_input_dict(batch: Dict):

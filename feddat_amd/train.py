@@ -5,6 +5,7 @@ src/train/main.py) on the MI355X engine.
   TaskTrainer.train_step(model, step, batch, optimizer, scheduler)  -> loss_0     task_trainer.py:266-330
   TaskTrainer.create_optimizer(model)  -> handle           task_trainer.py:477-504
   TaskTrainer.eval(model)              -> [score_gated, score_adapter0, score_adapter1]   task_trainer.py:211-246
+                                          (optimizer_mode adapter: one score, task_trainer.py:232-233)
   get_average_net(server, c_models, nums, ordered_tasks, device)   main.py:50-65   (feddat_amd.fedavg)
   main(argv)                           -> FL rounds x clients, same flags as main.py:262-323
 
@@ -25,6 +26,7 @@ from . import lib as L
 from . import vilt_spec
 from .fedavg import all_reduce_sum, allreduce_average, get_average_net  # noqa: F401  (re-exported: main.py:50)
 from .modeling import ViltContinualLearner, convert_batch_to_vilt_input_dict, create_vilt_continual_learner_model
+from .modes import mode_names
 
 
 class OptimizerHandle:
@@ -68,7 +70,8 @@ def kl_loss(output: torch.Tensor, target: torch.Tensor, temp: float = 3.0) -> to
 
 
 class TaskTrainer:
-    """VQATrainerCross + TaskTrainer for the dat optimizer_mode (train_vqa_crossvqa.py:39-239, task_trainer.py)."""
+    """VQATrainerCross + TaskTrainer for the dat and adapter optimizer_modes (train_vqa_crossvqa.py:39-239, task_trainer.py);
+    the mode is the model's (ViltContinualLearner.optimizer_mode)."""
 
     def __init__(self, args, task_key: str, train_batches: List[Dict[str, torch.Tensor]],
                  eval_batches: Optional[List[Dict[str, torch.Tensor]]] = None, logger=None):
@@ -107,11 +110,12 @@ class TaskTrainer:
             optimizer, num_warmup_steps=int(self.max_steps * self.warmup_ratio), num_training_steps=self.max_steps,
             lr_end=0, power=1)
         eng.lr, eng.eps, eng.wd = optimizer.lr, optimizer.eps, optimizer.weight_decay
-        # adapter_1 -> adapter_2 copy, freeze, fresh moments + schedule          task_trainer.py:36-59
+        # (dat: adapter_1 -> adapter_2 copy, freeze,) fresh moments + schedule          task_trainer.py:36-59
         eng.begin_local_update(self.task_key, steps_per_epoch=len(self.vqa_train_dataloader),
                                num_epochs=self.num_epochs, warmup_ratio=self.warmup_ratio,
                                opt_adapters=optimizer.adapters)
-        model.adapter_requires_grad[2] = False
+        if self._mode(model) == "dat":
+            model.adapter_requires_grad[2] = False
         if self.use_graph:
             eng.ensure_captured()      # before the upload worker below starts: capture never overlaps a prefetch
         loss = None
@@ -146,12 +150,20 @@ class TaskTrainer:
         else:
             eng.assert_finite()
 
+    @staticmethod
+    def _mode(model) -> str:
+        return getattr(model, "optimizer_mode", "dat")
+
     def train_step(self, model: ViltContinualLearner, step, batch, optimizer=None, scheduler=None, hooks=None,
                    epoch=None):
         """One DAT + MKD step; returns loss_0 (BCE * num_labels of the P2 pass) as a 0-d device tensor.  The mode
         switches the reference performs inside (activate_gating / set_active_adapter, task_trainer.py:284-312)
-        leave the model in the same final state: gating on, adapter_0 active."""
+        leave the model in the same final state: gating on, adapter_0 active.
+        optimizer_mode adapter: one forward / backward / AdamW step / scheduler tick (task_trainer.py:433-450); returns
+        loss = BCE * num_labels."""
         out = model.engine.train_step(self.encode_batch(model, batch), use_graph=self.use_graph)
+        if self._mode(model) == "adapter":
+            return out[0]
         model.activate_gating()
         model.set_active_adapter("adapter_0")
         return out[0]
@@ -171,6 +183,9 @@ class TaskTrainer:
 
     def eval(self, model: ViltContinualLearner):
         loader = self.vqa_test_dataloader
+        if self._mode(model) == "adapter":      # task_trainer.py:232-233,246: one score
+            model.set_active_adapter("adapter")
+            return self.eval_one_loader(model, loader)
         model.activate_gating()
         s = self.eval_one_loader(model, loader)
         model.deactivate_gating()
@@ -342,8 +357,11 @@ TASK_SETS = {   # main.py:352-359
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
-    if "dat" not in args.optimizer_mode:
-        raise L.FeddatHipError("only --optimizer_mode dat is on the MI355X hot path (SURVEY.md section 2, row 13)")
+    mode = "dat" if "dat" in args.optimizer_mode else args.optimizer_mode
+    if mode not in ("dat", "adapter"):
+        raise L.FeddatHipError("--optimizer_mode dat or adapter are on the MI355X hot path (SURVEY.md section 2, row 13)")
+    if mode == "adapter" and "albef" in args.encoder_name:
+        raise L.FeddatHipError("ALBEF supports only --optimizer_mode dat (adapter is a ViLT mode here)")
     logging.basicConfig(level=logging.INFO, format="%(asctime)s - %(levelname)s - %(message)s")
     log = logging.getLogger("feddat_amd")
     if args.mixed_precision is None:       # one default, the same as bench.py's and the engines' own
@@ -400,18 +418,21 @@ def main(argv=None):
         Trainer = AlbefTaskTrainer
     else:
         if pretrained:       # load_vilt_encoder (vilt.py:387-420): HF directory / state dict + modality-embedding expansion
-            params = weights.load_vilt_pretrained(pretrained, tasks, layers=args.num_layers, seed=args.seed)
+            params = weights.load_vilt_pretrained(pretrained, tasks, layers=args.num_layers, seed=args.seed, optimizer_mode=mode)
             log.info("loaded ViLT weights from %s", pretrained)
         else:                # no --pretrained_model_name: random weights of the real architecture (synthetic benchmarks)
-            params = vilt_spec.random_init(args.num_layers, tasks, seed=args.seed)
+            params = vilt_spec.random_init(args.num_layers, tasks, seed=args.seed, optimizer_mode=mode)
         model = create_vilt_continual_learner_model(params, tasks, dev, args.batch_size, args.image_size,
                                                     args.num_layers, args.lr,
-                                                    operands={"fp16": "f16", "bf16": "bf16"}[args.mixed_precision])
+                                                    operands={"fp16": "f16", "bf16": "bf16"}[args.mixed_precision],
+                                                    optimizer_mode=mode)
         Trainer = TaskTrainer
     eng = model.engine
-    # personal parameters per client (main.py:440-450): head + adapter_0 + adapter_2
+    # personal parameters per client (main.py:440-450): head + adapter_0 + adapter_2 (dat) / head (adapter)
     def personal(sd):
-        return {n: v.clone() for n, v in sd.items() if ("task" in n or "adapter_0" in n or "adapter_2" in n)}
+        keep = set(mode_names(list(sd), mode)["personal"])
+        return {n: v.clone() for n, v in sd.items() if n in keep}
+    comm_slot = 1 if mode == "dat" else 0       # the engine's adapter slot behind comm_flat()
     personal_params = {t: personal(model.state_dict()) for t in my_tasks}
     def make_batch(seed, ti=0):
         if albef:
@@ -457,7 +478,7 @@ def main(argv=None):
         nonfinite = []
         for k, task_key in enumerate(my_tasks):
             eng.comm_flat().copy_(server_flat)                      # main.py:472 deepcopy(server)
-            eng.repack_adapter(1)
+            eng.repack_adapter(comm_slot)
             model.load_state_dict(personal_params[task_key])        # main.py:473-478
             model.adapter_requires_grad = dict(server_flags)
             trainer = Trainer(args, task_key, data[task_key], data[task_key][:2], log)
@@ -491,7 +512,7 @@ def main(argv=None):
                 dist.barrier()          # every rank's personal files are on disk before round.json appears
             if rank == 0:
                 flags_after = dict(server_flags)
-                if comm_round % 5 == 0 or comm_round == args.comm_rounds - 1:
+                if mode == "dat" and (comm_round % 5 == 0 or comm_round == args.comm_rounds - 1):
                     flags_after.update({0: False, 1: True})         # the eval below leaves the server in this state
                 checkpoint.save_federation(args.output_dir, {n: sd[n] for n in comm_names}, {}, comm_round,
                                            server_flags=flags_after)
@@ -511,7 +532,7 @@ def main(argv=None):
             # (create_optimizer filters on requires_grad, task_trainer.py:477-504) no longer holds adapter_0.
             server_flags.update({0: False, 1: True})
     eng.comm_flat().copy_(server_flat)
-    eng.repack_adapter(1)
+    eng.repack_adapter(comm_slot)
     if rccl is not None:
         torch.cuda.synchronize()
         rccl.close()

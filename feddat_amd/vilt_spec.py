@@ -13,8 +13,10 @@ ENC = "vilt_encoder.vilt."
 
 def param_shapes(layers: int = 12, tasks: Sequence[str] = ("art",), hidden: int = 768, inter: int = 3072,
                  patch: int = 32, grid: int = 12, max_text: int = 40, vocab: int = 30522, num_labels: int = 100,
-                 bottleneck: int = 48) -> Dict[str, Tuple[int, ...]]:
+                 bottleneck: int = 48, optimizer_mode: str = "dat") -> Dict[str, Tuple[int, ...]]:
+    """optimizer_mode "dat": adapter_{0,1,2} in every layer; "adapter": the single `adapter` (main.py:114-118)."""
     H, I, r = hidden, inter, bottleneck
+    stems = {"dat": ("adapter_0_", "adapter_1_", "adapter_2_"), "adapter": ("adapter_",)}[optimizer_mode]
     s: Dict[str, Tuple[int, ...]] = {}
     e = ENC + "embeddings."
     s[e + "cls_token"] = (1, 1, H)
@@ -38,8 +40,8 @@ def param_shapes(layers: int = 12, tasks: Sequence[str] = ("art",), hidden: int 
         s[L + "intermediate.dense.bias"] = (I,)
         s[L + "output.layer.dense.weight"] = (H, I)
         s[L + "output.layer.dense.bias"] = (H,)
-        for a in range(3):
-            A = L + f"output.adapter.adapter_{a}_"
+        for stem in stems:
+            A = L + f"output.adapter.{stem}"
             s[A + "down.weight"] = (r, H)
             s[A + "down.bias"] = (r,)
             s[A + "up.weight"] = (H, r)
@@ -62,15 +64,18 @@ def param_shapes(layers: int = 12, tasks: Sequence[str] = ("art",), hidden: int 
 
 
 def random_init(layers: int = 12, tasks: Sequence[str] = ("art",), seed: int = 0, device="cpu",
-                std: float = 0.02, bias_std: float = 0.02) -> Dict[str, torch.Tensor]:
+                std: float = 0.02, bias_std: float = 0.02, optimizer_mode: str = "dat") -> Dict[str, torch.Tensor]:
     """BERT-style init (adapter.py:5-14: N(0, 0.02) weights, LayerNorm 1/0) -- biases get a small N(0, bias_std)
-    instead of exact zeros so that every bias path of the kernels is exercised."""
+    instead of exact zeros so that every bias path of the kernels is exercised.  optimizer_mode "adapter": the single adapter
+    per layer, with init_bert_weights' own zero biases."""
     g = torch.Generator(device=device)
     g.manual_seed(seed)
     out = {}
-    for k, shp in param_shapes(layers, tasks).items():
+    for k, shp in param_shapes(layers, tasks, optimizer_mode=optimizer_mode).items():
         is_ln = ("LayerNorm" in k) or ("layernorm" in k) or ("clf_norm0" in k)
-        if is_ln and k.endswith("weight"):
+        if optimizer_mode == "adapter" and ".adapter.adapter_" in k and k.endswith("bias"):
+            out[k] = torch.zeros(shp, device=device)
+        elif is_ln and k.endswith("weight"):
             out[k] = 1.0 + bias_std * torch.randn(shp, generator=g, device=device)
         elif k.endswith("bias"):
             out[k] = bias_std * torch.randn(shp, generator=g, device=device)

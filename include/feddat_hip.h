@@ -478,6 +478,20 @@ int feddat_step_tick_multi(int* const* states, const int* d_sched, const int* d_
  *   flags are cleared for the next step. */
 int feddat_dat_step_finish(int* head_state, int* ad1_state, int* ad0_state, int* flags, float* scaler_f, int* scaler_i,
                            float growth, float backoff, int growth_interval, hipStream_t stream);
+/* Single-adapter step (optimizer_mode adapter, task_trainer.py:433-450) -- additions within ABI 8:
+ * feddat_bce_loss_fwd_bwd: L = BCEWithLogits_mean(logits, target) * C in scalars[0] (numerically stable softplus form),
+ *   dlogits = dL/dlogits = (sigmoid(logits) - target) / B; logits / target / dlogits fp32 [B, C] (B <= 4096, any C), one launch,
+ *   fixed-order sums.  For C <= 128 scalars[0] is bit-equal to scalars[0] of feddat_dat_loss_fwd_bwd_single on the same inputs.
+ *   *nonfinite (DEVICE int, may be NULL) is OR-ed with 1 when L is inf / NaN.
+ * feddat_single_step_finish: end of one single-adapter train_step under a DYNAMIC loss scale, the one-step-per-batch
+ *   counterpart of feddat_dat_step_finish: applied = !*flag; every states[k] (n <= FEDDAT_ADAMW_MAX_GROUPS counters
+ *   {sched_t, adam_t}) += {applied, applied}; overflow -> scale *= backoff, tracker = 0, scaler_i[1] += 1, scaler_i[2] += 1;
+ *   else tracker += 1 and, once it reaches growth_interval, scale *= growth, tracker = 0; scale stays within [2^-14, 2^30];
+ *   scaler_f = {scale, 1 / scale}, scaler_i = {tracker, skipped sub-steps, skipped batches, reserved}; *flag is cleared. */
+int feddat_bce_loss_fwd_bwd(const float* logits, const float* target, int B, int C, float* dlogits, float* scalars,
+                            int* nonfinite, hipStream_t stream);
+int feddat_single_step_finish(int* const* states, int n, int* flag, float* scaler_f, int* scaler_i, float growth,
+                              float backoff, int growth_interval, hipStream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * K5  loss.  L = (BCEWithLogits_mean(logits,target) * C + 9 * KL_batchmean(log_softmax(logits/3) ||
