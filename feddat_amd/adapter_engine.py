@@ -50,7 +50,7 @@ class ViltAdapterEngine(ViltDatEngine):
         return L.make_segs([dict(row_begin=0, row_end=rows, adapters=[dict(self.ad16[0][layer], scale=1.0)])])
 
     def _wgrad_segs(self, layer: int, x, x_delta_s: int, dy):
-        key = ("wg", layer, x.data_ptr(), dy.data_ptr())
+        key = ("wg", layer, x.data_ptr(), dy.data_ptr(), self._dyn())
         if key not in self._segs_cache:
             n = self.ad_layer_numel
             self._segs_cache[key] = L.make_wgrad_segs([dict(x=x, dy=dy, z=self.z, dz=self.dz,
@@ -59,7 +59,7 @@ class ViltAdapterEngine(ViltDatEngine):
         return self._segs_cache[key]
 
     def _top_wgrad_segs(self):
-        key = ("wg-top",)
+        key = ("wg-top", self._dyn())
         if key not in self._segs_cache:
             i, n = self.nl - 1, self.ad_layer_numel
             self._segs_cache[key] = L.make_wgrad_segs([dict(x=self.top["h3"], dy=self.dcls, z=self.z, dz=self.dz,

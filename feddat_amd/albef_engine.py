@@ -357,7 +357,7 @@ class AlbefDatEngine:
 
     def _wgrad(self, m: int, mode: str, x, dy, rows: int):
         if mode == "both":       # adapter_0 from the gated half (scale 0.5), adapter_1 from the other; both are optimised here
-            key = ("wg2", m, x.data_ptr(), dy.data_ptr(), rows)
+            key = ("wg2", m, x.data_ptr(), dy.data_ptr(), rows, self.dynamic_scale)
             if key not in self._segs_cache:
                 n, h, g = self.ad_numel, rows // 2, self.gs["both"]
                 self._segs_cache[key] = L.make_wgrad_segs([
@@ -372,7 +372,7 @@ class AlbefDatEngine:
         a = 0 if mode == "gating" else int(mode.split("_")[1])
         if a not in self.opt_adapters:
             return
-        key = ("wg", m, a, x.data_ptr(), dy.data_ptr(), rows)
+        key = ("wg", m, a, x.data_ptr(), dy.data_ptr(), rows, self.dynamic_scale)
         if key not in self._segs_cache:
             n = self.ad_numel
             self._segs_cache[key] = L.make_wgrad_segs([dict(x=x, dy=dy, z=self.gs[mode]["z"], dz=self.gs[mode]["dz"],

@@ -201,7 +201,9 @@ __global__ __launch_bounds__(256, 2) void wgrad_kernel(WgradLaunch L) {   // 2 b
     }
 }
 
-// grad layer layout: [wd (R x H) | bd (R) | wu (H x R) | bu (H)]
+// grad layer layout: [wd (R x H) | bd (R) | wu (H x R) | bu (H)].  Returns whether a value it WROTE is inf / NaN (GradScaler's
+// inf check): in [R H, R H + R) su is the up problem's column sum of z, past it sd is the down problem's column sum of x --
+// by-products of the shared partial layout that are no gradient and are not checked.
 __device__ __forceinline__ bool wgrad_reduce_one(const float* __restrict__ partials, float* __restrict__ gl, int seg, int i) {
     const float* Pd = partials + (size_t)(2 * seg) * NBLK * PSTRIDE;       // dW_down problem
     const float* Pu = partials + (size_t)(2 * seg + 1) * NBLK * PSTRIDE;   // dW_up^T problem
@@ -215,12 +217,14 @@ __device__ __forceinline__ bool wgrad_reduce_one(const float* __restrict__ parti
         gl[i] = sd;                                   // wd[r][c]
         const int r = i / H, c = i - r * H;
         gl[R * H + R + (size_t)c * R + r] = su;       // wu[c][r] (transpose of the computed [r][c])
-    } else if (i < R * H + R) {
-        gl[i] = sd;                                   // bd[r] = sum dz
-    } else {
-        gl[R * H + R + H * R + (i - R * H - R)] = su;  // bu[c] = s * sum dy
+        return fd_nonfinite(sd) || fd_nonfinite(su);
     }
-    return !(fabsf(sd) <= 3.4e38f) || !(fabsf(su) <= 3.4e38f);      // inf / NaN in what was written (GradScaler's inf check)
+    if (i < R * H + R) {
+        gl[i] = sd;                                   // bd[r] = sum dz
+        return fd_nonfinite(sd);
+    }
+    gl[R * H + R + H * R + (i - R * H - R)] = su;     // bu[c] = s * sum dy
+    return fd_nonfinite(su);
 }
 
 __global__ __launch_bounds__(256) void wgrad_reduce_kernel(WgradLaunch L) {

@@ -212,7 +212,7 @@ __global__ void lm_loss_finish(const float* __restrict__ row_terms, int R, float
         scalars[0] = ce;
         scalars[1] = kl * kl_scale;
         scalars[2] = 0.5f * (ce + kl * kl_scale);
-        if (nonfinite && !(fabsf(ce + kl * kl_scale) <= 3.4e38f)) atomicOr(nonfinite, 1);      // GradScaler's inf check at its source
+        if (nonfinite && fd_nonfinite(ce + kl * kl_scale)) atomicOr(nonfinite, 1);      // GradScaler's inf check at its source
     }
 }
 

@@ -86,6 +86,8 @@ __device__ __forceinline__ float wave_max(float v) {
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
     return v;
 }
+// inf / NaN: GradScaler's inf check (torch.isfinite); every finite float up to FLT_MAX passes
+__device__ __forceinline__ bool fd_nonfinite(float x) { return !(fabsf(x) <= __FLT_MAX__); }
 
 // Counter-based dropout mask (ALBEF BERT towers, xbert.py:216,333,360,440): element `idx` of the tensor a site drops is
 // KEPT iff hash(idx; key0, key1, step) >= p * 2^32 -- two murmur3 finalisers with the keys injected; (key0, key1) name

@@ -427,7 +427,7 @@ __global__ __launch_bounds__(1024) void dat_loss_single_kernel(const float* __re
         scalars[1] = l_kl;
         scalars[2] = 0.5f * (l_bce + l_kl);
         // GradScaler's inf check, at its source: a non-finite loss means non-finite gradients in every parameter it reaches
-        if (nonfinite && !(fabsf(l_bce + l_kl) <= 3.4e38f)) atomicOr(nonfinite, 1);
+        if (nonfinite && fd_nonfinite(l_bce + l_kl)) atomicOr(nonfinite, 1);
     }
 }
 
@@ -461,7 +461,7 @@ __global__ __launch_bounds__(1024) void bce_loss_kernel(const float* __restrict_
     if (lane == 0) {
         const float l_bce = bce / (float)B;
         scalars[0] = l_bce;
-        if (nonfinite && !(fabsf(l_bce) <= 3.4e38f)) atomicOr(nonfinite, 1);
+        if (nonfinite && fd_nonfinite(l_bce)) atomicOr(nonfinite, 1);
     }
 }
 
@@ -566,16 +566,18 @@ __global__ void dat_step_finish_kernel(int* head_state, int* ad1_state, int* ad0
     ad1_state[1] += applied >= 1 ? 1 : 0;
     ad0_state[0] += applied;
     ad0_state[1] += applied == 2 ? 1 : 0;
-    float scale = scaler_f[0];
-    int tracker = scaler_i[0];
     if (applied < 2) {
-        scale = fmaxf(scale * backoff, 6.103515625e-05f);
-        tracker = 0;
         scaler_i[1] += 2 - applied;
         scaler_i[2] += 1;
-    } else {
-        tracker += 2;
-        if (tracker >= growth_interval) {
+    }
+    // GradScaler.update() once per backward, in the reference's order: sub-step A, then B
+    float scale = scaler_f[0];
+    int tracker = scaler_i[0];
+    for (const int found_inf : {fA, fB}) {
+        if (found_inf) {
+            scale = fmaxf(scale * backoff, 6.103515625e-05f);
+            tracker = 0;
+        } else if (++tracker >= growth_interval) {
             scale = fminf(scale * growth, 1073741824.0f);
             tracker = 0;
         }

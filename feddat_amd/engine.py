@@ -825,7 +825,7 @@ class ViltDatEngine:
 
     def _top_wgrad_segs(self):
         """Weight-gradient descriptor of the top layer's adapters (2B token-0 rows: adapter_0 | adapter_1)."""
-        key = ("wg-top", self.opt_adapters)
+        key = ("wg-top", self.opt_adapters, self._dyn())
         if key not in self._segs_cache:
             i, t, B, n = self.nl - 1, self.top, self.B, self.ad_layer_numel
             segs = [dict(x=t["h3"][r0:], dy=self.dcls[r0:], z=self.z[r0:], dz=self.dz[r0:],
@@ -858,7 +858,7 @@ class ViltDatEngine:
         return self._layer_structs[key]
 
     def _wgrad_segs(self, layer: int, x, x_delta_s: int, dy):
-        key = ("wg", layer, x.data_ptr(), dy.data_ptr(), self.opt_adapters)
+        key = ("wg", layer, x.data_ptr(), dy.data_ptr(), self.opt_adapters, self._dyn())
         if key not in self._segs_cache:
             R, n = self.R, self.ad_layer_numel
             segs = []

@@ -309,9 +309,9 @@ int feddat_adapter_wgrad_partial(const feddat_wgrad_seg* segs, int nseg, float* 
 int feddat_adapter_wgrad_reduce(float* const* grads_dev, int n, int nseg, const float* partials, long partials_stride,
                                 hipStream_t stream);
 /* ABI 8: the same reduction that also reports non-finite gradients -- nonfinite[s] (DEVICE int per segment) is OR-ed with 1
- * when any gradient element of segment s (any launch) is inf / NaN; it is never cleared here.  This is the inf check of
- * torch.cuda.amp.GradScaler.unscale_ (what accelerator.backward + optimizer.step run under fp16: task_trainer.py:302-308,
- * 323-328), made where the loss scale leaves the gradients. */
+ * when any gradient element of segment s (any launch) is inf / NaN (finite values up to FLT_MAX pass); it is never cleared
+ * here.  This is the inf check of torch.cuda.amp.GradScaler.unscale_ (what accelerator.backward + optimizer.step run under
+ * fp16: task_trainer.py:302-308, 323-328), made where the loss scale leaves the gradients. */
 int feddat_adapter_wgrad_reduce_checked(float* const* grads_dev, int n, int nseg, const float* partials, long partials_stride,
                                         int* nonfinite, hipStream_t stream);
 /* fp32 masters -> bf16 MFMA operand copies (r*H elements each).  All four are stored FRAGMENT-MAJOR -- the 64 lanes of
@@ -472,9 +472,12 @@ int feddat_step_tick_multi(int* const* states, const int* d_sched, const int* d_
  *   batch: B's forward already used A's head update -- DESIGN.md section 5b);
  *   counters {sched_t, adam_t}: head += {applied, applied}; adapter_1 += {applied, applied >= 1}; adapter_0 += {applied, applied == 2}
  *   (a skipped optimizer step skips its scheduler tick: accelerate/scheduler.py);
- *   scaler_f = {scale, 1 / scale}: any flag -> scale *= backoff (0.5), growth tracker = 0; else tracker += 2 and, once it reaches
- *   growth_interval, scale *= growth (2), tracker = 0 (GradScaler defaults: 65536 / 2 / 0.5 / 2000); scale stays within
- *   [2^-14, 2^30]; scaler_i = {tracker, skipped sub-steps so far, batches with a skip so far, reserved};
+ *   scaler_f = {scale, 1 / scale}: GradScaler.update() once per sub-step, A (flags[1]) then B (flags[0]), as the reference's two
+ *   sequential backwards run it: a set flag -> scale *= backoff (0.5), growth tracker = 0; a clear one -> tracker += 1 and, once it
+ *   reaches growth_interval, scale *= growth (2), tracker = 0 (GradScaler defaults: 65536 / 2 / 0.5 / 2000).  So both flags halve
+ *   twice, and growth may fall between A and B.  B's update reads flags[0] even when A voids the batch: the scale follows
+ *   GradScaler exactly, only the counters above follow the voided batch; scale stays within [2^-14, 2^30];
+ *   scaler_i = {tracker, skipped sub-steps so far (2 - applied per batch), batches with a skip so far, reserved};
  *   flags are cleared for the next step. */
 int feddat_dat_step_finish(int* head_state, int* ad1_state, int* ad0_state, int* flags, float* scaler_f, int* scaler_i,
                            float growth, float backoff, int growth_interval, hipStream_t stream);

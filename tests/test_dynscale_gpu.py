@@ -63,7 +63,7 @@ def test_no_overflow_is_bit_identical_to_the_static_scale(use_graph):
     assert st["scale"] == 16384.0 and st["growth_tracker"] == 2 * steps and st["skipped_substeps"] == 0
 
 
-@pytest.mark.parametrize("which,use_graph", [("B", False), ("B", True), ("A", False), ("A", True), ("AB", False)])
+@pytest.mark.parametrize("which,use_graph", [("B", False), ("B", True), ("A", False), ("A", True)])
 def test_injected_overflow_follows_gradscaler(which, use_graph):
     """The overflow flag of a sub-step is forced before step 2 (the flags are OR-ed into by the kernels and cleared by the end of
     the step, so a preset flag is an injected overflow); 5 steps; every trainable tensor against the oracle with the same skip."""
@@ -97,11 +97,20 @@ def test_injected_overflow_follows_gradscaler(which, use_graph):
         assert_update_parity(names, eng.state_dict(), P, P0, 1e-3, 0.06, f"{which} step {s + 1}")
     st = eng.scaler_state()
     applied = 2 * steps - (1 if which == "B" else 2)
-    assert st["scale"] == 8192.0 and st["skipped_batches"] == 1 and st["skipped_substeps"] == 2 * steps - applied
+    # GradScaler.update() per sub-step: one halving per overflowed sub-step (G15: both at once, 16384 -> 4096)
+    assert st["scale"] == (4096.0 if which == "AB" else 8192.0)
+    assert st["skipped_batches"] == 1 and st["skipped_substeps"] == 2 * steps - applied
     assert hp.state.tolist() == [applied, applied] and client.sched_t == applied
     assert eng.ad[1].state.tolist() == [applied, steps - (0 if which == "B" else 1)]
     assert eng.ad[0].state.tolist() == [applied + 1, steps - 1]
     assert eng.ovf_flags.tolist() == [0, 0]
+
+
+@pytest.mark.parametrize("use_graph", [False, True])
+def test_injected_overflow_in_both_substeps_halves_the_scale_twice(use_graph):
+    """A and B forced in one batch: the batch is void as for A alone, and GradScaler.update() runs once per overflowed
+    sub-step, so the scale halves twice (G15 step 5: 16384 -> 4096)."""
+    test_injected_overflow_follows_gradscaler("AB", use_graph)
 
 
 def test_a_scale_too_large_for_fp16_backs_off_and_training_continues():
