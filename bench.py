@@ -10,6 +10,11 @@
   `loss.npy` = the three values train_step returns (loss_0, KL, L_0: the head of its buffer; the rest of that buffer is kernel
   scratch, not output), `state.<key>.npy` = every trainable tensor it updated, under its state-dict key.
   The inputs are seeded, so the same arguments give the same inputs on every run and two builds compare file for file.
+  --full: after the headline figure, also measure what a plain run leaves out, each in runs of its own: the other 16-bit
+  operand format (`other_operand_format`, N = 1), the in-step roofline of the GEMMs and row kernels (`roofline`) and the CPU
+  baseline (`cpu_baseline`, N = 1); `--workload albef`: `roofline` and `cpu_baseline`.  --no-operand-ab / --no-roofline /
+  --no-cpu-baseline leave one of them out of a --full run.  A plain run only sets up, warms up, times the steps, writes
+  --dump-outputs and prints the line.
 
 A "step" is one full reference train_step (task_trainer.py:280-330: P0 + P1 + P2, two AdamW/scheduler steps) on one
 batch of B=32 synthetic 384x384 image / 40-token question pairs per client (BASELINE.json configs[1]; configs[2] for
@@ -570,12 +575,12 @@ def bench_albef(args, world, rank, dev, dist):
             out["per_rank"], out["round_split"] = rows, round_split(rows, dt, coll and coll.get("payload_bytes"))
         if dumped is not None:
             out["dump_outputs"] = dumped
-        if not args.no_roofline:
+        if args.full and not args.no_roofline:
             try:
                 out["roofline"] = albef_roofline(L, eng, batches)
             except Exception as e:
                 out["roofline"] = {"error": f"{type(e).__name__}: {e}"}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = albef_cpu_baseline()
             except Exception as e:
@@ -643,11 +648,15 @@ def main():
                          "default 0 is the deterministic configuration SURVEY.md 8d quotes config 4 in)")
     ap.add_argument("--unfused-tail", action="store_true",
                     help="A/B switch: the round-3 serial tail (46 single-purpose launches) instead of csrc/head_tail.hip")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline figure, also measure other_operand_format (N = 1), roofline and cpu_baseline (N = 1), "
+                         "each in runs of its own; a plain run prints the headline line only")
     ap.add_argument("--no-operand-ab", dest="no_operand_ab", action="store_true",
-                    help="skip the short run of the other 16-bit operand format that the N = 1 line carries as other_operand_format")
+                    help="with --full: skip the short run of the other 16-bit operand format that the N = 1 line carries as "
+                         "other_operand_format")
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip roofline")
     ap.add_argument("--host-input", action="store_true",
                     help="also time the same steps with batches starting in pinned HOST memory (PCIe-inclusive rate, "
                          "uploads overlapped by feddat_amd.data.DevicePrefetcher); reported as extra fields")
@@ -736,10 +745,10 @@ def main():
         host_ms = res_ms
     if not (loss == loss) or abs(loss) > 1e6:
         raise RuntimeError(f"non-finite loss {loss}")
-    # the OTHER 16-bit operand format on the same box, same batches, right behind the timed region (N = 1, default workload only):
-    # box-to-box spread is +-4 %, so the fp16 / bf16 ratio is only meaningful measured in one run
+    # --full: the OTHER 16-bit operand format on the same box, same batches, right behind the timed region (N = 1, default
+    # workload only): box-to-box spread is +-4 %, so the fp16 / bf16 ratio is only meaningful measured in one run
     other_fmt = None
-    if world == 1 and not args.fp8 and not args.no_operand_ab:
+    if args.full and world == 1 and not args.fp8 and not args.no_operand_ab:
         alt = "bf16" if eng.operands == "f16" else "f16"
         e2 = engine.ViltDatEngine(params, [task], dev, batch=B, res=res, layers=12, operands=alt)
         e2.fused_tail = eng.fused_tail
@@ -782,7 +791,9 @@ def main():
                 f"fp16-operand engine on the same round: 0.004, 0.2 %, 3.0e-4), batch={B}/client, ")
         else:
             workload = ("configs[1]" + (" with fp16 operands (BASELINE.json's configs[1] string says bf16: same operand width and MFMA "
-                                        "rate; the bf16 step is in other_operand_format)" if eng.operands == "f16" else "")
+                                        "rate; the bf16 step is in other_operand_format" + (")" if other_fmt is not None else
+                                                                                            " with --full)")
+                                        if eng.operands == "f16" else "")
                         + f": ViLT-B/32 FedDAT, 1 client per MI355X, {'fp16' if eng.operands == 'f16' else 'bf16'} MFMA operands"
                         + (f" (dynamic loss scale, GradScaler semantics on the device, initial 2^{int(math.log2(eng.loss_scale))})"
                            if eng.operands == "f16" and eng.scaler_state()["dynamic"] else
@@ -812,12 +823,12 @@ def main():
             out["per_rank"], out["round_split"] = rank_rows, round_split(rank_rows, dt, coll and coll.get("payload_bytes"))
         if dumped is not None:
             out["dump_outputs"] = dumped
-        if not args.no_roofline:
+        if args.full and not args.no_roofline:
             try:
                 out["roofline"] = roofline_block(L, eng, batches, gemms)
             except Exception as e:      # the throughput line must survive a failure of the auxiliary measurement
                 out["roofline"] = {"error": f"{type(e).__name__}: {e}"}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline({k: v.float().cpu() for k, v in params.items()},
                                                    [{k: v.cpu() for k, v in b.items()} for b in batches], B, res, task)

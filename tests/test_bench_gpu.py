@@ -1,6 +1,6 @@
 """`bench.py --dump-outputs DIR`: what the timed path computed in its last step, written so that two runs (or two builds) of the
 benchmark can be compared output for output.  Same arguments -> same inputs -> the same bits; and the files hold the state of
-the LAST timed step, not of anything bench.py runs after the timed region."""
+the LAST timed step, not of anything bench.py runs after the timed region.  And what a plain run leaves to `--full`."""
 import json
 import os
 import subprocess
@@ -15,12 +15,16 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 B, RES, STEPS, WARMUP = 4, 224, 3, 2
 
 
-def _bench(out_dir):
+def _run(*extra):
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(STEPS), "--warmup", str(WARMUP),
-           "--batch", str(B), "--res", str(RES), "--no-roofline", "--no-cpu-baseline", "--dump-outputs", str(out_dir)]
+           "--batch", str(B), "--res", str(RES), *extra]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     return json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+
+
+def _bench(out_dir):
+    return _run("--no-roofline", "--no-cpu-baseline", "--dump-outputs", str(out_dir))
 
 
 def _load(d):
@@ -64,3 +68,24 @@ def test_dump_outputs_repeat_bit_for_bit_and_hold_the_last_timed_step(tmp_path):
         assert np.abs(a["state." + k] - got).max() <= 1e-6, k
         moved += int(not np.array_equal(a["state." + k], init[k]))
     assert moved > 0
+
+
+AUX = ("other_operand_format", "roofline", "cpu_baseline")
+
+
+@pytest.mark.timeout(900)
+def test_plain_line_is_the_headline_and_full_adds_the_auxiliary_figures():
+    """A plain run prints the headline figures only; --full adds the other operand format, the in-step roofline and the CPU
+    baseline, each measured, not an error record."""
+    if not torch.cuda.is_available():
+        pytest.skip("needs a GPU")
+    plain = _run()
+    assert not set(AUX) & set(plain), sorted(plain)
+    full = _run("--full")
+    for k in ("metric", "unit", "higher_is_better", "dtype", "steps", "warmup"):
+        assert full[k] == plain[k], k
+    assert full["value"] > 0 and full["ms_per_step"] > 0
+    for k in AUX:
+        assert k in full and "error" not in full[k], (k, full.get(k))
+    assert full["other_operand_format"]["operands"] == "bf16" and full["other_operand_format"]["ms_per_step"] > 0
+    assert full["roofline"]["achieved"] > 0 and full["cpu_baseline"]["value"] > 0

@@ -160,6 +160,16 @@ def test_bench_help_renders():
     assert r.returncode == 0 and "--operands" in r.stdout, r.stderr[-500:]
 
 
+def test_bench_full_is_an_opt_in_switch():
+    """The auxiliary figures (other operand format, roofline, CPU baseline) sit behind --full, which is off by default."""
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--help"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "--full" in r.stdout, r.stderr[-500:]
+
+
 def test_bench_dump_outputs_writes_float32_arrays(tmp_path):
     """--dump-outputs: the returned loss values and every trainable tensor, whole, one float32 .npy each, under the 64 MB cap."""
     import numpy as np

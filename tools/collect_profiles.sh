@@ -1,10 +1,10 @@
 #!/usr/bin/env bash
-# Run on the GPU box (through gpurun) from the repo root: kernel-trace summary of the default bench command plus the
+# Run on a GPU box from the repo root: kernel-trace summary of the default bench command plus the
 # separate PMC passes (FETCH_SIZE / WRITE_SIZE / SQ set; counters in their own runs, --kernel-trace only), every pass under
-# its own timeout.  Outputs under gpurun_out/prof_$TAG; tools/summarize_profiles.py $TAG turns them into profiles/$TAG_*.csv.
+# its own timeout.  Outputs under evidence/prof_$TAG; tools/summarize_profiles.py $TAG turns them into profiles/$TAG_*.csv.
 TAG=${1:-r02}
 R=$(pwd)
-OUT=$R/gpurun_out/prof_$TAG
+OUT=$R/evidence/prof_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 timeout 600 rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o step --output-format csv -- \

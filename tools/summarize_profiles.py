@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Turn the rocprofv3 outputs under gpurun_out/ into the small per-round summaries kept under profiles/.
+"""Turn the rocprofv3 outputs under evidence/ into the small per-round summaries kept under profiles/.
    python tools/summarize_profiles.py r01
 """
 import collections
@@ -17,9 +17,9 @@ def short(n):
 
 
 # 1. kernel-trace --stats summary of one bench run
-st = f"gpurun_out/prof_{tag}/trace/step_kernel_stats.csv"
+st = f"evidence/prof_{tag}/trace/step_kernel_stats.csv"
 if not os.path.exists(st):
-    st = "gpurun_out/prof_r1/step_kernel_stats.csv"
+    st = "evidence/prof_r1/step_kernel_stats.csv"
 if os.path.exists(st):
     rows = list(csv.DictReader(open(st)))
     with open(f"profiles/{tag}_kernel_stats.csv", "w") as f:
@@ -36,9 +36,9 @@ if os.path.exists(st):
 # 2. PMC passes: per-kernel averages
 out = collections.defaultdict(lambda: collections.defaultdict(list))
 for d in ("pmc_sq_wave_cycles", "pmc_fetch_size", "pmc_write_size", "pmc_sq", "pmc_fetch", "pmc_write"):
-    p = f"gpurun_out/prof_{tag}/{d}/p_counter_collection.csv"
+    p = f"evidence/prof_{tag}/{d}/p_counter_collection.csv"
     if not os.path.exists(p):
-        p = f"gpurun_out/{d}/p_counter_collection.csv" if tag == "r01" else p
+        p = f"evidence/{d}/p_counter_collection.csv" if tag == "r01" else p
     if not os.path.exists(p):
         continue
     per_dispatch = collections.defaultdict(lambda: collections.defaultdict(float))
@@ -63,7 +63,7 @@ if out:
 
 
 # 3. ALBEF (configs[3]): kernel-trace summary + PMC passes of `bench.py --workload albef`
-st = f"gpurun_out/prof_{tag}/albef_trace/step_kernel_stats.csv"
+st = f"evidence/prof_{tag}/albef_trace/step_kernel_stats.csv"
 if os.path.exists(st):
     rows = list(csv.DictReader(open(st)))
     with open(f"profiles/{tag}_albef_kernel_stats.csv", "w") as f:
@@ -78,7 +78,7 @@ if os.path.exists(st):
     print("wrote", f"profiles/{tag}_albef_kernel_stats.csv")
 out = collections.defaultdict(lambda: collections.defaultdict(list))
 for d in ("albef_pmc_fetch_size", "albef_pmc_write_size"):
-    p = f"gpurun_out/prof_{tag}/{d}/p_counter_collection.csv"
+    p = f"evidence/prof_{tag}/{d}/p_counter_collection.csv"
     if not os.path.exists(p):
         continue
     per_dispatch = collections.defaultdict(lambda: collections.defaultdict(float))

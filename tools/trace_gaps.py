@@ -1,6 +1,6 @@
 """Timeline of ONE replayed step from a rocprofv3 --kernel-trace CSV: per kernel its duration and the idle gap in front of
 it, totals of busy / idle time, and the serial tail (everything between the last forward GEMM and the first backward
-attention).   python tools/trace_gaps.py gpurun_out/prof_r04/trace/step_kernel_trace.csv [--all]"""
+attention).   python tools/trace_gaps.py evidence/prof_r04/trace/step_kernel_trace.csv [--all]"""
 import csv
 import sys
 import collections
