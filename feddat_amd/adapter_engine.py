@@ -9,17 +9,19 @@ B samples (R = B * S rows) instead of 2 B, the same dynamic loss scale, and one 
 """
 from __future__ import annotations
 
-from typing import Dict, List, Optional, Sequence
+from typing import Dict, Optional, Sequence
 
 import torch
 
 from . import lib as L
-from .engine import ENC, FlatGroup, ViltDatEngine, _bound
+from .engine import ViltDatEngine
+from .local_update import _bound
 
 
 class ViltAdapterEngine(ViltDatEngine):
     NPASS = 1
     ADAPTER_STEMS = ("adapter_",)
+    COMM_ADAPTER = 0
 
     def __init__(self, params: Dict[str, torch.Tensor], tasks: Sequence[str], device, batch: int, res: int, fp8: bool = False,
                  **kw):
@@ -50,28 +52,18 @@ class ViltAdapterEngine(ViltDatEngine):
         return L.make_segs([dict(row_begin=0, row_end=rows, adapters=[dict(self.ad16[0][layer], scale=1.0)])])
 
     def _wgrad_segs(self, layer: int, x, x_delta_s: int, dy):
-        key = ("wg", layer, x.data_ptr(), dy.data_ptr(), self._dyn())
-        if key not in self._segs_cache:
-            n = self.ad_layer_numel
-            self._segs_cache[key] = L.make_wgrad_segs([dict(x=x, dy=dy, z=self.z, dz=self.dz,
-                                                            grad=self.ad[0].g[layer * n:(layer + 1) * n], rows=self.R,
-                                                            scale=1.0, **self._scale_out())])
-        return self._segs_cache[key]
+        n = self.ad_layer_numel
+        return self._wgrad_desc(("wg", layer, x.data_ptr(), dy.data_ptr()), lambda: [
+            dict(x=x, dy=dy, z=self.z, dz=self.dz, grad=self.ad[0].g[layer * n:(layer + 1) * n], rows=self.R, scale=1.0)])
 
     def _top_wgrad_segs(self):
-        key = ("wg-top", self._dyn())
-        if key not in self._segs_cache:
-            i, n = self.nl - 1, self.ad_layer_numel
-            self._segs_cache[key] = L.make_wgrad_segs([dict(x=self.top["h3"], dy=self.dcls, z=self.z, dz=self.dz,
-                                                            grad=self.ad[0].g[i * n:(i + 1) * n], rows=self.B, scale=1.0,
-                                                            **self._scale_out())])
-        return self._segs_cache[key]
+        i, n = self.nl - 1, self.ad_layer_numel
+        return self._wgrad_desc(("wg-top",), lambda: [
+            dict(x=self.top["h3"], dy=self.dcls, z=self.z, dz=self.dz, grad=self.ad[0].g[i * n:(i + 1) * n], rows=self.B,
+                 scale=1.0)])
 
-    def _trained_groups(self) -> List[FlatGroup]:
-        return [self.ad[0], self.head[self.task]]
-
-    def _trained_slots(self) -> Sequence[int]:
-        return (0,)
+    def _named_groups(self):
+        return [("adapter", self.ad[0]), ("head", self.head[self.task])]
 
     # ------------------------------------------------------------------------------------------ train step
     @_bound
@@ -80,22 +72,7 @@ class ViltAdapterEngine(ViltDatEngine):
         """TaskTrainer.train prologue for optimizer_mode adapter (task_trainer.py:36-59): no teacher copy; a fresh AdamW over
         adapter + head and a fresh poly schedule over steps_per_epoch * num_epochs ticks (one tick per batch)."""
         self.task = task
-        total = steps_per_epoch * num_epochs
-        self.sched = dict(total=total, warmup=int(total * warmup_ratio))
-        for grp in (self.ad[0], self.head[task]):
-            grp.m.zero_()
-            grp.v.zero_()
-            grp.g.zero_()
-            grp.state.zero_()
-        # a fresh GradScaler per local update (main.py:435: a fresh Accelerator per round)
-        self.scaler_f.copy_(torch.tensor([self.loss_scale, 1.0 / self.loss_scale], dtype=torch.float32))
-        self.scaler_i.zero_()
-        self.ovf_flags.zero_()
-        sig = (task, total, self.sched["warmup"], self.lr, self.wd, self.eps, self.use_layer_calls, self.fused_tail,
-               self.cls_attention, self.operands, self.loss_scale, self._dyn(), self.scale_growth_interval, self.top_q_cls)
-        if getattr(self, "_graph_sig", None) != sig:
-            self.graph = None
-            self._graph_sig = sig
+        self._start_local_update(steps_per_epoch, num_epochs, warmup_ratio, {})
 
     @_bound
     def _step_kernels(self):
@@ -118,18 +95,9 @@ class ViltAdapterEngine(ViltDatEngine):
         else:
             L.step_tick_multi([self.ad[0].state, hp.state], [1, 1], [1, 1])
 
-    @_bound
-    def train_step(self, batch: Optional[Dict[str, torch.Tensor]] = None, use_graph: bool = False):
-        """One single-adapter step (task_trainer.py:433-450).  Returns the device tensor whose [0] is what the reference
-        returns: loss = BCE_mean * num_labels."""
-        if batch is not None:
-            self.set_batch(batch)
-        if not use_graph:
-            self._step_kernels()
-        else:
-            if self.graph is None:
-                self._capture()
-            self.graph.replay()
+    def _loss_tensor(self):
+        """What train_step returns (task_trainer.py:433-450): the device tensor whose [0] is the reference's loss =
+        BCE_mean * num_labels."""
         return self.loss_out
 
     # ------------------------------------------------------------------------------------------ inference / state
@@ -140,21 +108,3 @@ class ViltAdapterEngine(ViltDatEngine):
     def repack(self):
         """fp32 master adapter -> 16-bit MFMA operand copies (after a load / FedAvg write-back)."""
         self.repack_adapter(0)
-
-    @_bound
-    def load_tensors(self, tensors: Dict[str, torch.Tensor]):
-        sd = self.state_dict()
-        touched = False
-        for n, v in tensors.items():
-            sd[n].copy_(v.to(self.dev, torch.float32))
-            touched = touched or n.startswith(ENC)
-        if touched:
-            self.repack_adapter(0)
-
-    def comm_flat(self) -> torch.Tensor:
-        """The FedAvg payload: every adapter tensor back-to-back in state-dict order (main.py:154-163)."""
-        return self.ad[0].p
-
-    def nonfinite_groups(self):
-        return [name for name, grp in (("adapter", self.ad[0]), ("head", self.head[self.task]))
-                if not bool(torch.isfinite(grp.p).all())]

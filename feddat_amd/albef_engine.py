@@ -25,19 +25,18 @@ reference's 0.1 (--albef_dropout).
 """
 from __future__ import annotations
 
-import math
 from typing import Dict, List, Optional, Sequence
 
 import torch
 
 from . import lib as L
-from .engine import FlatGroup, _bound
+from .local_update import FlatGroup, LocalUpdateEngine, _bound
 
 PRE = "albef_model.albef."
 ADAPTER_TENSORS = ("down.weight", "down.bias", "up.weight", "up.bias")
 
 
-class AlbefDatEngine:
+class AlbefDatEngine(LocalUpdateEngine):
     def __init__(self, params: Dict[str, torch.Tensor], device, batch: int, n_answers: int, q_len: int = 25, a_len: int = 4,
                  vit_depth: int = 12, enc_layers: int = 12, fusion_layer: int = 6, dec_layers: int = 6, image: int = 384,
                  vocab: int = 30522, lr: float = 1e-4, weight_decay: float = 1e-2, adam_eps: float = 1e-8, pad_id: int = 0,
@@ -53,17 +52,10 @@ class AlbefDatEngine:
         and ..._seed8800.npz) fp16 operands land at 3.2e-4 / 2.6e-4 on the worst adapter element (mean ratio 0.005 / 0.003), bf16
         operands at 7.6e-4 / 8.4e-4 (0.024 / 0.028): both inside north_star's 1e-3, bf16 with a fifth of it to spare, for 1.5 % of
         the step (tests/test_sizes_gpu.py::test_albef_full_size_round_of_40_steps_vs_reference_golden asserts all four)."""
-        if operands not in L.OPERAND_DTYPE:
-            raise L.FeddatHipError(f"operands must be 'bf16' or 'f16', got {operands!r}")
-        self.operands, self.op_dtype = operands, L.OPERAND_DTYPE[operands]
-        # fp16 operands: the loss scale is dynamic by default -- GradScaler on the device exactly as in ViltDatEngine (DESIGN.md
-        # section 5b).  The LM head is frozen here, so the two sub-steps share no trainable tensor: flag B (adapter_0's pass)
-        # skips adapter_0's step alone; flag A (adapter_1's pass) voids the batch like in the ViLT engine (one finish kernel).
-        self.dynamic_scale = bool(operands == "f16" if dynamic_loss_scale is None else dynamic_loss_scale)
-        self.scale_growth_interval = int(scale_growth_interval)
-        self.loss_scale = float(loss_scale if loss_scale is not None else (16384.0 if operands == "f16" else 1.0))
-        if self.loss_scale <= 0 or math.frexp(self.loss_scale)[0] != 0.5:
-            raise L.FeddatHipError("loss_scale must be a power of two (it is removed exactly)")
+        # fp16 operands: the loss scale is dynamic by default -- LocalUpdateEngine's GradScaler on the device, as in ViltDatEngine
+        # (DESIGN.md section 5b).  The LM head is frozen here, so the two sub-steps share no trainable tensor: flag B (adapter_0's
+        # pass) skips adapter_0's step alone; flag A (adapter_1's pass) voids the batch like in the ViLT engine (one finish kernel).
+        self._init_loss_scale(operands, loss_scale, dynamic_loss_scale, scale_growth_interval)
         with L.operands(operands):
             self._init(params, device, batch, n_answers, q_len, a_len, vit_depth, enc_layers, fusion_layer, dec_layers, image, vocab,
                        lr, weight_decay, adam_eps, pad_id, max_pos, dropout, seed, stack_text)
@@ -204,10 +196,7 @@ class AlbefDatEngine:
             self.wpart_stride2 = L.adapter_wgrad_workspace_elems(2)
             self.wpart["both"] = torch.empty(len(self.modules) * self.wpart_stride2, device=dev)
         self.side = None           # second stream of train_step (created lazily on the engine's device)
-        self.scaler_f = torch.tensor([self.loss_scale, 1.0 / self.loss_scale], dtype=torch.float32, device=self.dev)
-        self.scaler_i = torch.zeros(4, dtype=torch.int32, device=self.dev)
-        self.ovf_flags = torch.zeros(2, dtype=torch.int32, device=self.dev)      # {B: adapter_0's pass, A: adapter_1's pass}
-        self._no_head = torch.zeros(2, dtype=torch.int32, device=self.dev)       # feddat_dat_step_finish's head counters: none here
+        self._alloc_scaler()
         self.drop_ctr = torch.zeros(2, dtype=torch.int32, device=dev)      # [0] = train_steps since begin_local_update
         self._alloc()
         if self.dropout > 0:       # teacher logits of P0: the gated text pass is re-run (other masks) for P2
@@ -357,29 +346,23 @@ class AlbefDatEngine:
 
     def _wgrad(self, m: int, mode: str, x, dy, rows: int):
         if mode == "both":       # adapter_0 from the gated half (scale 0.5), adapter_1 from the other; both are optimised here
-            key = ("wg2", m, x.data_ptr(), dy.data_ptr(), rows, self.dynamic_scale)
-            if key not in self._segs_cache:
-                n, h, g = self.ad_numel, rows // 2, self.gs["both"]
-                self._segs_cache[key] = L.make_wgrad_segs([
-                    dict(x=x, dy=dy, z=g["z"], dz=g["dz"], grad=self.ad[0].g[m * n:(m + 1) * n], rows=h, scale=0.5,
-                         **self._scale_out()),
-                    dict(x=x[h:], dy=dy[h:], z=g["z"][h:], dz=g["dz"][h:], grad=self.ad[1].g[m * n:(m + 1) * n], rows=h, scale=1.0,
-                         **self._scale_out())])
+            n, h, g = self.ad_numel, rows // 2, self.gs["both"]
+            segs = self._wgrad_desc(("wg2", m, x.data_ptr(), dy.data_ptr(), rows), lambda: [
+                dict(x=x, dy=dy, z=g["z"], dz=g["dz"], grad=self.ad[0].g[m * n:(m + 1) * n], rows=h, scale=0.5),
+                dict(x=x[h:], dy=dy[h:], z=g["z"][h:], dz=g["dz"][h:], grad=self.ad[1].g[m * n:(m + 1) * n], rows=h, scale=1.0)])
             ws = self.wpart_stride2
-            L.adapter_wgrad_partial(self._segs_cache[key], self.wpart["both"][m * ws:(m + 1) * ws])
+            L.adapter_wgrad_partial(segs, self.wpart["both"][m * ws:(m + 1) * ws])
             self._wg_done["both"].append(m)
             return
         a = 0 if mode == "gating" else int(mode.split("_")[1])
         if a not in self.opt_adapters:
             return
-        key = ("wg", m, a, x.data_ptr(), dy.data_ptr(), rows, self.dynamic_scale)
-        if key not in self._segs_cache:
-            n = self.ad_numel
-            self._segs_cache[key] = L.make_wgrad_segs([dict(x=x, dy=dy, z=self.gs[mode]["z"], dz=self.gs[mode]["dz"],
-                                                            grad=self.ad[a].g[m * n:(m + 1) * n], rows=rows,
-                                                            scale=0.5 if mode == "gating" else 1.0, **self._scale_out())])
+        n = self.ad_numel
+        segs = self._wgrad_desc(("wg", m, a, x.data_ptr(), dy.data_ptr(), rows), lambda: [
+            dict(x=x, dy=dy, z=self.gs[mode]["z"], dz=self.gs[mode]["dz"], grad=self.ad[a].g[m * n:(m + 1) * n], rows=rows,
+                 scale=0.5 if mode == "gating" else 1.0)])
         ws = self.wpart_stride
-        L.adapter_wgrad_partial(self._segs_cache[key], self.wpart[mode][m * ws:(m + 1) * ws])
+        L.adapter_wgrad_partial(segs, self.wpart[mode][m * ws:(m + 1) * ws])
         self._wg_done[mode].append(m)
 
     def _wgrad_reduce(self, mode: str):
@@ -396,10 +379,8 @@ class AlbefDatEngine:
                 ptrs = [self.ad[a].g[m * n:(m + 1) * n].data_ptr() for m in ms for a in (0, 1)]
                 self._segs_cache[key] = torch.tensor(ptrs, dtype=torch.int64, device=self.dev)
             ws = self.wpart_stride2
-            if self.dynamic_scale:      # segments (adapter_0, adapter_1) = flags (B, A)
-                L.adapter_wgrad_reduce_checked(self._segs_cache[key], len(ms), 2, self.wpart["both"][ms[0] * ws:], ws, self.ovf_flags)
-            else:
-                L.adapter_wgrad_reduce(self._segs_cache[key], len(ms), 2, self.wpart["both"][ms[0] * ws:], ws)
+            # segments (adapter_0, adapter_1) = flags (B, A)
+            self._reduce_wgrads(self._segs_cache[key], len(ms), 2, self.wpart["both"][ms[0] * ws:], ws, self.ovf_flags)
             return
         a = 0 if mode == "gating" else int(mode.split("_")[1])
         ms = tuple(sorted(done))
@@ -410,35 +391,20 @@ class AlbefDatEngine:
             ptrs = torch.tensor([self.ad[a].g[m * n:(m + 1) * n].data_ptr() for m in ms], dtype=torch.int64, device=self.dev)
             self._segs_cache[key] = (ptrs, contiguous)
         ptrs, contiguous = self._segs_cache[key]
-        ws = self.wpart_stride
-        red = (lambda *a_: L.adapter_wgrad_reduce_checked(*a_, self.ovf_flags[a:a + 1])) if self.dynamic_scale else L.adapter_wgrad_reduce
+        ws, flag = self.wpart_stride, self.ovf_flags[a:a + 1]
         if contiguous:       # the usual case (all 30 modules): slots m0 .. m0 + len - 1 are one strided batch
-            red(ptrs, len(ms), 1, self.wpart[mode][ms[0] * ws:], ws)
+            self._reduce_wgrads(ptrs, len(ms), 1, self.wpart[mode][ms[0] * ws:], ws, flag)
         else:
             for j, m in enumerate(ms):
-                red(ptrs[j:j + 1], 1, 1, self.wpart[mode][m * ws:], ws)
-
-    def _scale_out(self):
-        """How the loss scale leaves, where the adapter weight gradients are formed (engine.ViltDatEngine._scale_out)."""
-        return dict(grad_unscale=1.0, grad_unscale_dev=self.scaler_f[1:2]) if self.dynamic_scale else \
-            dict(grad_unscale=1.0 / self.loss_scale)
+                self._reduce_wgrads(ptrs[j:j + 1], 1, 1, self.wpart[mode][m * ws:], ws, flag)
 
     def _scale_in(self, mode: str):
-        """... and how it enters, on dL/dlogits of the pass `mode` (+ that pass's overflow flag for a non-finite loss)."""
-        if not self.dynamic_scale:
+        """How the loss scale enters, on dL/dlogits of the pass `mode` (+ that pass's overflow flag for a non-finite loss); it
+        leaves through LocalUpdateEngine._scale_out."""
+        if not self._dyn():
             return dict(grad_scale=self.loss_scale)
         a = 0 if mode == "gating" else 1
         return dict(grad_scale=1.0, grad_scale_dev=self.scaler_f[0:1], nonfinite=self.ovf_flags[a:a + 1])
-
-    def scaler_state(self) -> Dict[str, float]:
-        """Host copy of the loss scaler (one device read-back): current scale, growth tracker, skipped sub-steps / batches."""
-        f, i = self.scaler_f.tolist(), self.scaler_i.tolist()
-        return dict(scale=f[0], growth_tracker=i[0], skipped_substeps=i[1], skipped_batches=i[2], dynamic=self.dynamic_scale)
-
-    @_bound
-    def copy_global_to_teacher(self):
-        self.ad[2].p.copy_(self.ad[1].p)
-        self.repack_adapter(2)
 
     _KINDS = {"emb": 0, "self_probs": 1, "self_out": 2, "cross_probs": 3, "cross_out": 4, "out": 5}
 
@@ -796,33 +762,19 @@ class AlbefDatEngine:
         every client draws its own masks -- like the reference's nn.Dropout, which keeps consuming the global RNG across
         rounds and clients -- and a resumed run reproduces them without any saved RNG state."""
         self.copy_global_to_teacher()
-        total = steps_per_epoch * num_epochs
-        self.sched = dict(total=total, warmup=int(total * warmup_ratio))
         self.opt_adapters = tuple(opt_adapters)
-        for grp in (self.ad[0], self.ad[1]):
-            grp.m.zero_()
-            grp.v.zero_()
-            grp.g.zero_()
-        self.ad[1].state.copy_(torch.tensor([0, 0], dtype=torch.int32))       # adapter_1 is stepped at tick 2b
-        self.ad[0].state.copy_(torch.tensor([1, 0], dtype=torch.int32))       # adapter_0 at tick 2b + 1
         self.drop_ctr.copy_(torch.tensor([(int(dropout_epoch) << 16) & 0x7FFFFFFF, 0], dtype=torch.int32))
-        # a fresh GradScaler per local update (the reference builds a fresh Accelerator per round: main.py:435)
-        self.scaler_f.copy_(torch.tensor([self.loss_scale, 1.0 / self.loss_scale], dtype=torch.float32))
-        self.scaler_i.zero_()
-        self.ovf_flags.zero_()
-        # a captured step stays valid across local updates as long as everything it froze into kernel arguments or into its
-        # launch list is unchanged (all mutable state -- weights, moments, counters -- lives in device buffers)
-        sig = (total, self.sched["warmup"], self.opt_adapters, self.lr, self.wd, self.eps, self.dropout, self.batch_text,
-               self.operands, self.loss_scale, self.dynamic_scale, self.scale_growth_interval)
-        if getattr(self, "_graph_sig", None) != sig:
-            self.graph = None
-            self._graph_sig = sig
+        # adapter_1 is stepped at tick 2b, adapter_0 at tick 2b + 1
+        self._start_local_update(steps_per_epoch, num_epochs, warmup_ratio, {"adapter_0": (1, 0)})
 
-    def _adamw(self, grp: FlatGroup):
-        if not hasattr(grp, "_wdv"):
-            grp._wdv = grp.seg_wd * self.wd
-        L.adamw_flat(grp.p, grp.g, grp.m, grp.v, grp.seg_off, grp._wdv, grp.state, self.lr, self.sched["warmup"],
-                     self.sched["total"], 0.9, 0.98, self.eps)
+    def _graph_switches(self):
+        return (self.dropout, self.batch_text)
+
+    def _named_groups(self):
+        return [("adapter_0", self.ad[0]), ("adapter_1", self.ad[1])]
+
+    def _extra_step_state(self):
+        return [self.drop_ctr]
 
     @_bound
     def _step_kernels(self):
@@ -886,85 +838,14 @@ class AlbefDatEngine:
         self._optimizer_tail(drop)
 
     def _optimizer_tail(self, drop: bool):
-        if self.dynamic_scale:
-            # GradScaler's skips as device predicates (engine.ViltDatEngine._step_kernels; here without a head): adapter_1 stays on
-            # flag A, adapter_0 on either flag; feddat_dat_step_finish ticks the counters by what was applied, updates the scale and
-            # clears the flags
-            fB, fA = self.ovf_flags[0:1], self.ovf_flags[1:2]
-
-            def grp(a, skip):
-                G = self.ad[a]
-                if not hasattr(G, "_wdv"):
-                    G._wdv = G.seg_wd * self.wd
-                return L.adamw_group(G.p, G.g, G.m, G.v, G.seg_off, G._wdv, G.state, skip_if=skip)
-            groups = ([grp(1, (fA,))] if 1 in self.opt_adapters else []) + ([grp(0, (fA, fB))] if 0 in self.opt_adapters else [])
-            if groups:
-                L.adamw_multi(groups, self.lr, self.sched["warmup"], self.sched["total"], 0.9, 0.98, self.eps)
-            for a in (1, 0):
-                if a in self.opt_adapters:
-                    self.repack_adapter(a)
-            L.dat_step_finish(self._no_head, self.ad[1].state, self.ad[0].state, self.ovf_flags, self.scaler_f, self.scaler_i,
-                              2.0, 0.5, self.scale_growth_interval)
-            if drop:
-                L.step_tick(self.drop_ctr, 1, 0)
-            return
-        if 1 in self.opt_adapters:
-            self._adamw(self.ad[1])
-            self.repack_adapter(1)
-        L.step_tick(self.ad[1].state, 2, 1)
-        if 0 in self.opt_adapters:
-            self._adamw(self.ad[0])
-            self.repack_adapter(0)
-        L.step_tick(self.ad[0].state, 2, 1)
+        self._dat_tail()        # the DAT tail without a head
         if drop:
             L.step_tick(self.drop_ctr, 1, 0)                 # the next train_step draws fresh masks (also under graph replay)
 
-    @_bound
-    def train_step(self, batch: Optional[Dict] = None, use_graph: bool = False):
-        """One DAT + MKD step; returns the device buffer {loss_0, kl_0, L_0} of the P2 pass (the reference returns loss_0).
-        use_graph: replay the ~3000 launches of a step as one hipGraph (the BERT towers' launches are tiny: eager mode is
-        host-bound)."""
-        if batch is not None:
-            self.set_batch(batch)
-        if not use_graph:
-            self._step_kernels()
-        else:
-            if self.graph is None:
-                self._capture()
-            self.graph.replay()
+    def _loss_tensor(self):
+        """What train_step returns: the device buffer {loss_0, kl_0, L_0} of the P2 pass (the reference returns loss_0).  A
+        step is ~3000 launches (the BERT towers' are tiny: without use_graph the step is host-bound)."""
         return self.acts["gating"]["loss"]
-
-    @_bound
-    def _capture(self):
-        """Capture the whole step into one hipGraph (static buffers; schedule and Adam counters live on the device); the
-        optimizer state is saved / restored around the warm-up + capture run so that capturing does not advance training."""
-        groups = [self.ad[0], self.ad[1]]
-        saved = [(g.p.clone(), g.m.clone(), g.v.clone(), g.state.clone()) for g in groups]
-        saved_ctr = self.drop_ctr.clone()
-        saved_scaler = (self.scaler_f.clone(), self.scaler_i.clone(), self.ovf_flags.clone())
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            self._step_kernels()
-        torch.cuda.current_stream().wait_stream(s)
-        torch.cuda.synchronize()
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph, capture_error_mode="thread_local"):
-            self._step_kernels()
-        torch.cuda.synchronize()
-        for g, (p, m, v, st) in zip(groups, saved):
-            g.p.copy_(p)
-            g.m.copy_(m)
-            g.v.copy_(v)
-            g.state.copy_(st)
-        self.drop_ctr.copy_(saved_ctr)
-        self.scaler_f.copy_(saved_scaler[0])
-        self.scaler_i.copy_(saved_scaler[1])
-        self.ovf_flags.copy_(saved_scaler[2])
-        for a in (0, 1):
-            self.repack_adapter(a)
-        torch.cuda.synchronize()
-        self.graph = graph
 
     # ------------------------------------------------------------------------------------------ inference
     @_bound
@@ -1033,37 +914,3 @@ class AlbefDatEngine:
         out = torch.empty(self.Mi, self.H, device=self.dev)
         L.layernorm_fwd(V["out"], self.vit["ng"], self.vit["nb"], 1e-6, self.Mi, self.H, y_f32=out)
         return out.view(self.B, self.Ni, self.H)
-
-    # ------------------------------------------------------------------------------------------ state dict
-    def state_dict(self) -> Dict[str, torch.Tensor]:
-        return {n: grp.view(n) for grp in self.ad for n in grp.names}
-
-    @_bound
-    def load_tensors(self, tensors: Dict[str, torch.Tensor]):
-        sd = self.state_dict()
-        touched = set()
-        for n, v in tensors.items():
-            sd[n].copy_(v.to(self.dev, torch.float32))
-            touched.update(a for a in range(3) if f"adapter_{a}_" in n)
-        for a in touched:
-            self.repack_adapter(a)
-
-    def assert_finite(self):
-        """As ViltDatEngine.assert_finite -- the last line of defence: with the dynamic loss scale (default for operands='f16') an
-        overflowed sub-step is skipped on the device and this never fires; with a static scale (dynamic_loss_scale=False) one host
-        read-back of the trainable adapters per local update turns an overflow into an error that names the knob."""
-        bad = self.nonfinite_groups()
-        if bad:
-            raise L.FeddatHipError(
-                f"non-finite values in {', '.join(bad)} after the local update: with operands={self.operands!r} the backward carries a "
-                f"{'dynamic' if self.dynamic_scale else 'static'} loss scale (initial value {self.loss_scale:g}); construct the engine "
-                "with dynamic_loss_scale=True, a smaller power of two (loss_scale=...) or operands='bf16' (this engine's default)")
-
-    def nonfinite_groups(self):
-        """Names of the trainable groups holding an inf / NaN (one host read-back each); [] = all finite (train.main agrees on
-        this across ranks before the FedAvg collective)."""
-        return [f"adapter_{a}" for a in (0, 1) if not bool(torch.isfinite(self.ad[a].p).all())]
-
-    def comm_flat(self) -> torch.Tensor:
-        """The FedAvg payload: all adapter_1 tensors of the 30 modules back-to-back (2 236 320 floats = 8.95 MB)."""
-        return self.ad[1].p

@@ -17,13 +17,13 @@ Restructuring relative to the reference (same results, fewer FLOPs -- DESIGN.md 
 """
 from __future__ import annotations
 
-import functools
 import math
-from typing import Dict, List, Optional, Sequence
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 
 from . import lib as L
+from .local_update import FlatGroup, LocalUpdateEngine, _bound
 
 ENC = "vilt_encoder.vilt."
 ADAPTER_TENSORS = ("down.weight", "down.bias", "up.weight", "up.bias")
@@ -31,49 +31,7 @@ HEAD_TENSORS = ("clf_fc0.weight", "clf_fc0.bias", "clf_norm0.weight", "clf_norm0
                 "clf_fc1.bias")
 
 
-def _no_decay(name: str) -> bool:  # task_trainer.py:478
-    return ("bias" in name) or ("LayerNorm.weight" in name)
-
-
-def _bound(fn):
-    """Run a public engine method with the calling thread bound to the library of the engine's operand format
-    (lib.operands): engines of both formats can live in one process."""
-    @functools.wraps(fn)
-    def wrapped(self, *a, **kw):
-        with L.operands(self.operands):
-            return fn(self, *a, **kw)
-    return wrapped
-
-
-class FlatGroup:
-    """A set of named fp32 tensors living back-to-back in one flat device buffer (+ grad, Adam m/v, segment table)."""
-
-    def __init__(self, names_shapes: Sequence, device, with_opt: bool):
-        self.names = [n for n, _ in names_shapes]
-        self.shapes = {n: tuple(s) for n, s in names_shapes}
-        self.offsets = {}
-        off = 0
-        for n, s in names_shapes:
-            self.offsets[n] = off
-            off += int(math.prod(s))
-        self.numel = off
-        self.p = torch.zeros(off, device=device)
-        if with_opt:
-            self.g = torch.zeros(off, device=device)
-            self.m = torch.zeros(off, device=device)
-            self.v = torch.zeros(off, device=device)
-            offs = [self.offsets[n] for n in self.names] + [off]
-            self.seg_off = torch.tensor(offs, dtype=torch.int64, device=device)
-            self.seg_wd = torch.tensor([0.0 if _no_decay(n) else 1.0 for n in self.names], device=device)
-            self.state = torch.zeros(2, dtype=torch.int32, device=device)  # {sched_t, adam_t}
-
-    def view(self, name: str, buf: Optional[torch.Tensor] = None) -> torch.Tensor:
-        buf = self.p if buf is None else buf
-        o = self.offsets[name]
-        return buf[o:o + int(math.prod(self.shapes[name]))].view(self.shapes[name])
-
-
-class ViltDatEngine:
+class ViltDatEngine(LocalUpdateEngine):
     # passes per sample through the backbone: the DAT step runs the gated and the adapter_1 pass as one batch of 2 B samples
     NPASS = 2
     # state-dict stems of the engine's adapters (adapter.py:22-58): slot a <-> "...output.adapter.<stem>{down,up}.{weight,bias}"
@@ -96,7 +54,7 @@ class ViltDatEngine:
         1e-4 .. 1e1 at the default, eleven binades inside either end of fp16's range.
         dynamic_loss_scale (default: on with "f16" operands): the reference's GradScaler (accelerate, mixed_precision fp16:
         accelerate_config.yaml:8; task_trainer.py:302-308,323-328) ON THE DEVICE, inside the captured step -- `loss_scale` is
-        only the initial value (GradScaler's own is 65536); a non-finite adapter gradient (feddat_adapter_wgrad_reduce_checked)
+        only the initial value (GradScaler's own is 65536); a non-finite adapter gradient (the checked weight-gradient reduce)
         or loss (feddat_dat_loss_fwd_bwd_checked) skips that sub-step's optimizer AND scheduler step and halves the scale,
         `scale_growth_interval` clean sub-steps double it (feddat_dat_step_finish; DESIGN.md section 5b says where this
         differs from GradScaler: an overflow in sub-step A voids the whole batch).  With no overflow the step is bit-identical
@@ -113,21 +71,13 @@ class ViltDatEngine:
         round from 1.31e-3 to 1.00e-3 and the worst update-norm error from 2.9 % to 1.6 % -- for callers
         that trade 2 % of throughput for that."""
         operands = operands or ("bf16" if fp8 else "f16")
-        if operands not in L.OPERAND_DTYPE:
-            raise L.FeddatHipError(f"operands must be 'bf16' or 'f16', got {operands!r}")
         if fp8 and operands != "bf16":
             raise L.FeddatHipError("fp8=True (configs[4]) pairs the e4m3 products with bf16 operands")
-        self.operands = operands
-        self.op_dtype = L.OPERAND_DTYPE[operands]
-        self.loss_scale = float(loss_scale if loss_scale is not None else (16384.0 if operands == "f16" else 1.0))
-        if self.loss_scale <= 0 or math.frexp(self.loss_scale)[0] != 0.5:
-            raise L.FeddatHipError("loss_scale must be a power of two (it is removed exactly)")
+        self._init_loss_scale(operands, loss_scale, dynamic_loss_scale, scale_growth_interval)
         # fp8 (round 5): the attention backward writes dq | dk | dv as MX-scaled e4m3 (one E8M0 scale per (row, 32 columns):
         # feddat_attn_bwd_fp8mx) and QKV^T runs on the block-scaled fp8 MFMA with those scales (feddat_gemm_fp8mx_nt): the seventh
         # of the eight frozen products per layer, and half the bytes of the backward's largest write
         self.fp8_mx_dqkv = bool(fp8) and bool(fp8_mx_dqkv)
-        self.dynamic_scale = bool(operands == "f16" if dynamic_loss_scale is None else dynamic_loss_scale)
-        self.scale_growth, self.scale_backoff, self.scale_growth_interval = 2.0, 0.5, int(scale_growth_interval)
         self._init(params, tasks, device, batch, res, text_len, layers, num_labels, lr, weight_decay, adam_eps, wgrad_splits,
                    fp8, fp8_ffn_chain, gelu_codes)
 
@@ -357,12 +307,9 @@ class ViltDatEngine:
         self.sched = dict(warmup=1, total=2)
         self.opt_adapters = (0, 1)
         self.task = self.tasks[0]
-        # dynamic loss scale (GradScaler on the device): {scale, 1 / scale}; {growth tracker, skipped sub-steps, batches with a
-        # skip, -}; overflow flags {sub-step B = adapter_0 pass, sub-step A = adapter_1 pass}; the head's p | m | v before its
-        # sub-step-A update (restored when A turns out to have overflowed in the backbone's backward)
-        self.scaler_f = torch.tensor([self.loss_scale, 1.0 / self.loss_scale], dtype=torch.float32, device=dev)
-        self.scaler_i = torch.zeros(4, dtype=torch.int32, device=dev)
-        self.ovf_flags = torch.zeros(2, dtype=torch.int32, device=dev)
+        # dynamic loss scale (GradScaler on the device); the head's p | m | v before its sub-step-A update (restored when A
+        # turns out to have overflowed in the backbone's backward)
+        self._alloc_scaler()
         self.head_bak = {t: torch.empty(3 * self.head[t].p.numel(), device=dev) for t in self.tasks} if self.dynamic_scale else {}
 
     # ------------------------------------------------------------------------------------------ adapters
@@ -393,12 +340,6 @@ class ViltDatEngine:
         else:
             for p in packs:
                 L.adapter_pack(p["wd32"], p["wu32"], p["wd"], p["wdT"], p["wu"], p["wuT"])
-
-    @_bound
-    def copy_global_to_teacher(self):
-        """adapter_1 -> adapter_2 at the start of every local update (task_trainer.py:36-41)."""
-        self.ad[2].p.copy_(self.ad[1].p)
-        self.repack_adapter(2)
 
     def _segs(self, layer: int, first: bool, bwd: bool):
         """Two-segment descriptor: rows [0,R) gated (adapter_0 + adapter_2, 0.5 each), rows [R,2R) adapter_1."""
@@ -700,14 +641,9 @@ class ViltDatEngine:
         self._sg(self.da0, 2 * H, 1, hp.view(pre + "clf_fc0.weight"), H, 1, B, H, 2 * H, dpooled_out, ksplit=8)
 
     def _adamw(self, grp: FlatGroup):
+        """One group's AdamW as its own launch (the unfused tail)."""
         L.adamw_flat(grp.p, grp.g, grp.m, grp.v, grp.seg_off, self._wd_vec(grp), grp.state, self.lr,
                      self.sched["warmup"], self.sched["total"], 0.9, 0.98, self.eps)
-
-    def _wd_vec(self, grp: FlatGroup):
-        if not hasattr(grp, "_wdv") or grp._wdv_val != self.wd:
-            grp._wdv = grp.seg_wd * self.wd
-            grp._wdv_val = self.wd
-        return grp._wdv
 
     # ------------------------------------------------------------------------------------------ backward
     @_bound
@@ -825,14 +761,10 @@ class ViltDatEngine:
 
     def _top_wgrad_segs(self):
         """Weight-gradient descriptor of the top layer's adapters (2B token-0 rows: adapter_0 | adapter_1)."""
-        key = ("wg-top", self.opt_adapters, self._dyn())
-        if key not in self._segs_cache:
-            i, t, B, n = self.nl - 1, self.top, self.B, self.ad_layer_numel
-            segs = [dict(x=t["h3"][r0:], dy=self.dcls[r0:], z=self.z[r0:], dz=self.dz[r0:],
-                         grad=self.ad[ad].g[i * n:(i + 1) * n], rows=B, scale=sc, **self._scale_out())
-                    for ad, r0, sc in ((0, 0, 0.5), (1, B, 1.0)) if ad in self.opt_adapters]
-            self._segs_cache[key] = L.make_wgrad_segs(segs) if segs else None
-        return self._segs_cache[key]
+        i, t, B, n = self.nl - 1, self.top, self.B, self.ad_layer_numel
+        return self._wgrad_desc(("wg-top", self.opt_adapters), lambda: [
+            dict(x=t["h3"][r0:], dy=self.dcls[r0:], z=self.z[r0:], dz=self.dz[r0:], grad=self.ad[ad].g[i * n:(i + 1) * n],
+                 rows=B, scale=sc) for ad, r0, sc in ((0, 0, 0.5), (1, B, 1.0)) if ad in self.opt_adapters])
 
     def _layer_struct(self, i: int):
         """ctypes views of layer i's frozen weights and static activation buffers for the composite entry points."""
@@ -858,16 +790,11 @@ class ViltDatEngine:
         return self._layer_structs[key]
 
     def _wgrad_segs(self, layer: int, x, x_delta_s: int, dy):
-        key = ("wg", layer, x.data_ptr(), dy.data_ptr(), self.opt_adapters, self._dyn())
-        if key not in self._segs_cache:
-            R, n = self.R, self.ad_layer_numel
-            segs = []
-            for a, row0, xrow0, sc in ((0, 0, 0, 0.5), (1, R, R + x_delta_s, 1.0)):
-                if a in self.opt_adapters:
-                    segs.append(dict(x=x[xrow0:], dy=dy[row0:], z=self.z[row0:], dz=self.dz[row0:],
-                                     grad=self.ad[a].g[layer * n:(layer + 1) * n], rows=R, scale=sc, **self._scale_out()))
-            self._segs_cache[key] = L.make_wgrad_segs(segs) if segs else None
-        return self._segs_cache[key]
+        R, n = self.R, self.ad_layer_numel
+        return self._wgrad_desc(("wg", layer, x.data_ptr(), dy.data_ptr(), self.opt_adapters), lambda: [
+            dict(x=x[xrow0:], dy=dy[row0:], z=self.z[row0:], dz=self.dz[row0:], grad=self.ad[a].g[layer * n:(layer + 1) * n],
+                 rows=R, scale=sc)
+            for a, row0, xrow0, sc in ((0, 0, 0, 0.5), (1, R, R + x_delta_s, 1.0)) if a in self.opt_adapters])
 
     def _wpart(self, layer: int):
         return self.wpart_all[layer * self.wpart_stride:(layer + 1) * self.wpart_stride]
@@ -882,29 +809,17 @@ class ViltDatEngine:
             n = self.ad_layer_numel
             ptrs = [self.ad[a].g[i * n:(i + 1) * n].data_ptr() for i in range(self.nl) for a in ads]
             self._segs_cache[key] = torch.tensor(ptrs, dtype=torch.int64, device=self.dev)
-        if self._dyn():      # + GradScaler's inf check where the loss scale leaves the gradients: flags[a] for adapter a
-            L.adapter_wgrad_reduce_checked(self._segs_cache[key], self.nl, len(ads), self.wpart_all, self.wpart_stride,
-                                           self.ovf_flags[ads[0]:])
-        else:
-            L.adapter_wgrad_reduce(self._segs_cache[key], self.nl, len(ads), self.wpart_all, self.wpart_stride)
+        # flags[a] for adapter a
+        self._reduce_wgrads(self._segs_cache[key], self.nl, len(ads), self.wpart_all, self.wpart_stride, self.ovf_flags[ads[0]:])
 
     def _dyn(self) -> bool:
         """Dynamic loss scale in effect (it rides on the fused tail's multi-group AdamW launch)."""
         return self.dynamic_scale and self.fused_tail
 
     def _scale_in(self):
-        """How the loss scale enters the backbone's backward (factor of the pooler-backward product)."""
+        """How the loss scale enters the backbone's backward (factor of the pooler-backward product); it leaves through
+        _scale_out."""
         return dict(alpha=1.0, alpha_dev=self.scaler_f[0:1]) if self._dyn() else dict(alpha=self.loss_scale)
-
-    def _scale_out(self):
-        """... and how it leaves, where the adapter weight gradients are formed."""
-        return dict(grad_unscale=1.0, grad_unscale_dev=self.scaler_f[1:2]) if self._dyn() else \
-            dict(grad_unscale=1.0 / self.loss_scale)
-
-    def scaler_state(self) -> Dict[str, float]:
-        """Host copy of the loss scaler (one device read-back): current scale, growth tracker, skipped sub-steps / batches."""
-        f, i = self.scaler_f.tolist(), self.scaler_i.tolist()
-        return dict(scale=f[0], growth_tracker=i[0], skipped_substeps=i[1], skipped_batches=i[2], dynamic=self._dyn())
 
     def _adapter_wgrads(self, layer: int, x, x_delta_s: int, dy):
         """dW_up = s dy^T z, db_up = s sum_t dy, dW_down = dz^T x, db_down = sum_t dz (autograd of adapter.py:125-146)
@@ -921,35 +836,19 @@ class ViltDatEngine:
         """TaskTrainer.train prologue (task_trainer.py:36-59): teacher snapshot, fresh AdamW state and schedule."""
         self.task = task
         self.copy_global_to_teacher()
-        total = steps_per_epoch * num_epochs
-        self.sched = dict(total=total, warmup=int(total * warmup_ratio))
         self.opt_adapters = tuple(opt_adapters)
-        for grp in (self.ad[0], self.ad[1], self.head[task]):
-            grp.m.zero_()
-            grp.v.zero_()
-            grp.g.zero_()
         # scheduler index / Adam step count per group: adapter_1 is stepped at 2b, adapter_0 at 2b+1, head at both
-        self.ad[1].state.copy_(torch.tensor([0, 0], dtype=torch.int32))
-        self.ad[0].state.copy_(torch.tensor([1, 0], dtype=torch.int32))
-        self.head[task].state.copy_(torch.tensor([0, 0], dtype=torch.int32))
-        # a fresh GradScaler per local update (the reference builds a fresh Accelerator per round: main.py:435)
-        self.scaler_f.copy_(torch.tensor([self.loss_scale, 1.0 / self.loss_scale], dtype=torch.float32))
-        self.scaler_i.zero_()
-        self.ovf_flags.zero_()
-        # a captured step stays valid across local updates as long as everything it froze into kernel arguments or into its
-        # launch list is unchanged (all mutable state -- weights, moments, counters -- lives in device buffers)
-        sig = (task, total, self.sched["warmup"], self.opt_adapters, self.lr, self.wd, self.eps, self.use_layer_calls, self.fp8,
-               self.fp8_ffn_chain, self.fused_tail, self.cls_attention, self.operands, self.loss_scale, self.fp8_mx_dqkv,
-               self._dyn(), self.scale_growth_interval, self.top_q_cls)        # host-side switches that change the launch list are part of the signature
-        if getattr(self, "_graph_sig", None) != sig:
-            self.graph = None
-            self._graph_sig = sig
+        self._start_local_update(steps_per_epoch, num_epochs, warmup_ratio, {"adapter_0": (1, 0)})
 
-    def _adamw_group(self, grp: FlatGroup, d_sched: int = 0, d_adam: int = 0, **kw):
-        return L.adamw_group(grp.p, grp.g, grp.m, grp.v, grp.seg_off, self._wd_vec(grp), grp.state, d_sched, d_adam, **kw)
+    def _graph_switches(self) -> Tuple:
+        return (self.task, self.use_layer_calls, self.fp8, self.fp8_ffn_chain, self.fused_tail, self.cls_attention,
+                self.fp8_mx_dqkv, self.top_q_cls)
 
-    def _adamw_many(self, groups):
-        L.adamw_multi(groups, self.lr, self.sched["warmup"], self.sched["total"], 0.9, 0.98, self.eps)
+    def _named_groups(self):
+        return [("adapter_0", self.ad[0]), ("adapter_1", self.ad[1]), ("head", self.head[self.task])]
+
+    def _state_groups(self):
+        return self.ad + list(self.head.values())
 
     def _loss(self, logits, teacher, slot):
         if self._dyn():      # + non-finite loss -> the sub-step's overflow flag (p1 = sub-step A, p2 = B)
@@ -973,9 +872,8 @@ class ViltDatEngine:
         logits_all, logits_1 = logits_both[:B], logits_both[B:]
         self._loss(logits_1, logits_all, "p1")
         self._head_bwd(pooled_s, "p1", task, self.dpooled[B:])
-        dyn = self._dyn()
-        fB, fA = self.ovf_flags[0:1], self.ovf_flags[1:2]
-        if dyn:      # sub-step A's head update: skipped on a non-finite loss; the old p | m | v are kept for the restore below
+        if self._dyn():      # sub-step A's head update: skipped on a non-finite loss; the old p | m | v are kept for the restore below
+            fA = self.ovf_flags[1:2]
             self._adamw_many([self._adamw_group(hp, skip_if=(fA,), bak=self.head_bak[task], bak_mode=1)])
         elif self.fused_tail:
             self._adamw_many([self._adamw_group(hp)])       # sub-step 2b; its counters are ticked once, at the end of the step
@@ -988,29 +886,8 @@ class ViltDatEngine:
         self._head_bwd(pooled_g, "p2", task, self.dpooled[:B])
         # one backward for both passes, then the deferred adapter_1 step (lr index 2b) and the P2 steps (2b+1)
         self._backward_dual()
-        if self.fused_tail:
-            # adapter_1 (2b), head (2b + 1: reads its counters one ahead), adapter_0 (2b + 1) in ONE launch, then the bf16
-            # operand copies, then ONE tick for all counters
-            if dyn:
-                # GradScaler's skips as device predicates: A overflowed (flag A) -> nothing of this batch is applied: adapter_1
-                # and adapter_0 stay, the head returns to its state before sub-step A; only B overflowed -> A stands, the head's
-                # second update and adapter_0's are skipped.  feddat_dat_step_finish ticks the counters by what was applied
-                # (a skipped optimizer step skips its scheduler tick), updates the scale and clears the flags.
-                groups = ([self._adamw_group(self.ad[1], skip_if=(fA,))] if 1 in self.opt_adapters else []) + \
-                    [self._adamw_group(hp, 1, 1, skip_if=(fB,), bak=self.head_bak[task], bak_mode=2, restore_if=fA)] + \
-                    ([self._adamw_group(self.ad[0], skip_if=(fA, fB))] if 0 in self.opt_adapters else [])
-            else:
-                groups = ([self._adamw_group(self.ad[1])] if 1 in self.opt_adapters else []) + [self._adamw_group(hp, 1, 1)] + \
-                    ([self._adamw_group(self.ad[0])] if 0 in self.opt_adapters else [])
-            self._adamw_many(groups)
-            for a in (1, 0):
-                if a in self.opt_adapters:
-                    self.repack_adapter(a)
-            if dyn:
-                L.dat_step_finish(hp.state, self.ad[1].state, self.ad[0].state, self.ovf_flags, self.scaler_f, self.scaler_i,
-                                  self.scale_growth, self.scale_backoff, self.scale_growth_interval)
-            else:
-                L.step_tick_multi([hp.state, self.ad[1].state, self.ad[0].state], [2, 2, 2], [2, 1, 1])
+        if self.fused_tail:      # the shared DAT tail, with the head (restored from head_bak when sub-step A overflowed)
+            self._dat_tail(hp, self.head_bak.get(task))
             return
         if 1 in self.opt_adapters:
             self._adamw(self.ad[1])
@@ -1023,88 +900,10 @@ class ViltDatEngine:
             self.repack_adapter(0)
         L.step_tick(self.ad[0].state, 2, 1)
 
-    @_bound
-    def train_step(self, batch: Optional[Dict[str, torch.Tensor]] = None, use_graph: bool = False):
-        """One DAT+MKD step (task_trainer.py:280-330).  Returns the device tensor holding what the reference
-        returns: loss_0 = BCE * num_labels of the P2 pass (loss_buf['p2'][0]); [1] = KL, [2] = L_0."""
-        if batch is not None:
-            self.set_batch(batch)
-        if not use_graph:
-            self._step_kernels()
-        else:
-            if self.graph is None:
-                self._capture()
-            self.graph.replay()
+    def _loss_tensor(self):
+        """What train_step returns: the device tensor holding what the reference returns, loss_0 = BCE * num_labels of the
+        P2 pass (loss_buf['p2'][0]); [1] = KL, [2] = L_0."""
         return self.loss_buf["p2"]
-
-    @_bound
-    def ensure_captured(self):
-        """Capture the step graph now if it is not there yet (TaskTrainer.train calls this before it starts the upload
-        worker, so no capture ever overlaps a prefetch)."""
-        if self.graph is None:
-            self._capture()
-
-    @_bound
-    def _capture(self):
-        """Capture the whole step into one hipGraph (all launches are on static buffers; the LR schedule and Adam
-        step counts live on the device).  The optimizer state is saved/restored around the warm-up + capture
-        run so that capturing does not advance training."""
-        groups = self._trained_groups()
-        saved = [(g.p.clone(), g.m.clone(), g.v.clone(), g.state.clone()) for g in groups]
-        saved_scaler = (self.scaler_f.clone(), self.scaler_i.clone(), self.ovf_flags.clone())
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            self._step_kernels()      # warm-up (sets function attributes, allocates lazily created scratch)
-        torch.cuda.current_stream().wait_stream(s)
-        torch.cuda.synchronize()
-        graph = torch.cuda.CUDAGraph()
-        # thread_local: other host threads (feddat_amd.data.DevicePrefetcher's upload worker) may allocate and copy on their
-        # own streams while this thread captures; the default global mode would turn their hipMalloc / hipMemcpy into
-        # hipErrorStreamCaptureUnsupported
-        with torch.cuda.graph(graph, capture_error_mode="thread_local"):
-            self._step_kernels()
-        torch.cuda.synchronize()
-        for g, (p, m, v, st) in zip(groups, saved):
-            g.p.copy_(p)
-            g.m.copy_(m)
-            g.v.copy_(v)
-            g.state.copy_(st)
-        self.scaler_f.copy_(saved_scaler[0])
-        self.scaler_i.copy_(saved_scaler[1])
-        self.ovf_flags.copy_(saved_scaler[2])
-        for a in self._trained_slots():
-            self.repack_adapter(a)
-        torch.cuda.synchronize()
-        self.graph = graph
-
-    def _trained_groups(self) -> List[FlatGroup]:
-        """The groups a train_step updates (saved and restored around the capture)."""
-        return [self.ad[0], self.ad[1], self.head[self.task]]
-
-    def _trained_slots(self) -> Sequence[int]:
-        return (0, 1)
-
-    def assert_finite(self):
-        """Last line of defence.  With the dynamic loss scale (the default for fp16 operands) an overflowed sub-step is skipped
-        on the device like GradScaler does (task_trainer.py:302 via accelerate) and this never fires; with a STATIC scale
-        (dynamic_loss_scale=False, or the unfused tail) a gradient operand that left fp16's range turns the update non-finite.
-        One host read-back of the trainable state, meant to be called once per local update (TaskTrainer.train does; train.main
-        agrees on the outcome across ranks BEFORE the FedAvg collective); raises with what to change."""
-        bad = self.nonfinite_groups()
-        if bad:
-            raise L.FeddatHipError(
-                f"non-finite values in {', '.join(bad)} after the local update: with operands={self.operands!r} the backward "
-                f"carries a {'dynamic' if self._dyn() else 'static'} loss scale (initial value {self.loss_scale:g}); "
-                + ("the scaler skips overflowed steps, so the non-finite values entered through the inputs or the weights"
-                   if self._dyn() else
-                   "this model's gradients leave fp16's range at that scale -- construct the engine with "
-                   "dynamic_loss_scale=True, a smaller power of two (loss_scale=...) or operands='bf16'"))
-
-    def nonfinite_groups(self):
-        """Names of the trainable groups holding an inf / NaN (one host read-back each); [] = all finite."""
-        return [name for name, grp in (("adapter_0", self.ad[0]), ("adapter_1", self.ad[1]), ("head", self.head[self.task]))
-                if not bool(torch.isfinite(grp.p).all())]
 
     # ------------------------------------------------------------------------------------------ inference
     @_bound
@@ -1127,28 +926,3 @@ class ViltDatEngine:
         self._pool(h, B)
         logits = self._head_fwd(self.pooled[:B], "all", task)
         return self.pooled[:B].clone(), logits.clone()
-
-    # ------------------------------------------------------------------------------------------ state dict
-    def state_dict(self) -> Dict[str, torch.Tensor]:
-        """Trainable tensors under the reference's state-dict keys (views into the flat buffers)."""
-        out = {}
-        for grp in self.ad + list(self.head.values()):
-            for n in grp.names:
-                out[n] = grp.view(n)
-        return out
-
-    @_bound
-    def load_tensors(self, tensors: Dict[str, torch.Tensor]):
-        sd = self.state_dict()
-        touched = set()
-        for n, v in tensors.items():
-            sd[n].copy_(v.to(self.dev, torch.float32))
-            for a in range(3):
-                if f"adapter_{a}_" in n:
-                    touched.add(a)
-        for a in touched:
-            self.repack_adapter(a)
-
-    def comm_flat(self) -> torch.Tensor:
-        """The FedAvg payload: all adapter_1 tensors back-to-back in state-dict order (main.py:154-163,499-503)."""
-        return self.ad[1].p
