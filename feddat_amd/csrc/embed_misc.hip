@@ -107,6 +107,14 @@ __global__ __launch_bounds__(256) void image_assemble_kernel(const float* __rest
     *reinterpret_cast<f32x4*>(h + ((size_t)b * S + Lt + t) * H + c * 4) = o;
 }
 
+// The bilinear blend of the masked position-grid resize, shared by pos_resize_masked_kernel and image_assemble_masked_kernel
+// with FMA contraction off: left to the compiler, the scalar and the 4-wide copies of this expression were contracted
+// differently, so the fused launch was not bit-identical with the separate ones for padded images (ly, lx != 0).
+__device__ __forceinline__ float fd_bilerp(float v00, float v01, float v10, float v11, float ly, float lx) {
+#pragma clang fp contract(off)
+    return (1.f - ly) * ((1.f - lx) * v00 + lx * v01) + ly * ((1.f - lx) * v10 + lx * v11);
+}
+
 // bilinear, align_corners=True: src = dst * (g - 1) / (gdst - 1)
 __global__ __launch_bounds__(256) void pos_resize_kernel(const float* __restrict__ grid, float* __restrict__ out,
                                                          int g, int gh, int gw, int H) {
@@ -159,7 +167,7 @@ __global__ __launch_bounds__(256) void pos_resize_masked_kernel(const float* __r
         const float ly = sy - (float)y0, lx = sx - (float)x0;
         const float v00 = grid[((size_t)y0 * g + x0) * H + c], v01 = grid[((size_t)y0 * g + x1) * H + c];
         const float v10 = grid[((size_t)y1 * g + x0) * H + c], v11 = grid[((size_t)y1 * g + x1) * H + c];
-        v = (1.f - ly) * ((1.f - lx) * v00 + lx * v01) + ly * ((1.f - lx) * v10 + lx * v11);
+        v = fd_bilerp(v00, v01, v10, v11, ly, lx);
     }
     out[(size_t)b * gh * gw * H + i] = v;
 }
@@ -223,7 +231,7 @@ __global__ __launch_bounds__(256) void image_assemble_masked_kernel(const float*
             const f32x4 v11 = *reinterpret_cast<const f32x4*>(grid + ((size_t)y1 * g + x1) * H + c * 4);
 #pragma unroll
             for (int e = 0; e < 4; ++e)
-                v[e] = (1.f - ly) * ((1.f - lx) * v00[e] + lx * v01[e]) + ly * ((1.f - lx) * v10[e] + lx * v11[e]);
+                v[e] = fd_bilerp(v00[e], v01[e], v10[e], v11[e], ly, lx);
         }
         o = (*reinterpret_cast<const f32x4*>(proj + ((size_t)b * np + p) * H + c * 4) + v) + m4;
     }

@@ -27,7 +27,10 @@ def _dev(b):
     return {k: (v.to(DEV) if isinstance(v, torch.Tensor) else v) for k, v in b.items()}
 
 
-@pytest.mark.parametrize("n,p,step", [(75 * 768, 0.1, 0), (800 * 768, 0.1, 7), (4 * 768, 0.5, 3)])
+DROPOUT_SHAPES = [(75 * 768, 0.1, 0), (800 * 768, 0.1, 7), (4 * 768, 0.5, 3)]
+
+
+@pytest.mark.parametrize("n,p,step", DROPOUT_SHAPES)
 def test_dropout_kernel_is_the_oracle_mask_bit_for_bit(L, n, p, step):
     g = torch.Generator().manual_seed(n)
     x = torch.randn(n, generator=g)
@@ -51,13 +54,16 @@ def test_dropout_kernel_is_the_oracle_mask_bit_for_bit(L, n, p, step):
     assert abs(float(keep.float().mean()) - (1 - p)) < 5 * (p * (1 - p) / n) ** 0.5
 
 
-@pytest.mark.parametrize("B,Sq,Skv,heads,causal,masked", [
+ATTN2_DROPOUT_SHAPES = [
     (3, 25, 25, 12, False, True),        # text self-attention, padded questions
     (5, 7, 7, 12, True, True),           # decoder: causal + padded answers
     (5, 7, 25, 12, False, True),         # decoder -> question cross-attention
     (2, 25, 577, 12, False, False),      # text encoder -> 577 image tokens (streamed K / V, 128-key dK/dV blocks)
     (2, 130, 70, 2, True, False),        # 128-query blocks (QT = 2 on the query side)
-])
+]
+
+
+@pytest.mark.parametrize("B,Sq,Skv,heads,causal,masked", ATTN2_DROPOUT_SHAPES)
 def test_attn2_dropout_fwd_bwd_vs_fp32_reference(L, B, Sq, Skv, heads, causal, masked):
     p, step = 0.1, 3
     k0, k1 = L.dropout_keys(5, 1, 9)

@@ -168,7 +168,10 @@ def test_gemm_rejects_bad_shapes(L):
 
 
 # ------------------------------------------------------------------ K3 LayerNorm
-@pytest.mark.parametrize("rows,H", [(37, 768), (5920, 768), (64, 1536)])
+LAYERNORM_SHAPES = [(37, 768), (5920, 768), (64, 1536)]
+
+
+@pytest.mark.parametrize("rows,H", LAYERNORM_SHAPES)
 def test_layernorm_fwd_bwd(L, rows, H):
     g = torch.Generator().manual_seed(rows)
     x = (torch.randn(rows, H, generator=g) * 2 + 0.3).to(DEV)
@@ -521,7 +524,10 @@ def test_sgemm_f32(L, I, J, K, ksplit):
     assert (out2.double() - A.double() @ Bm.double()).abs().max() < 2e-5 * math.sqrt(K) * 4
 
 
-@pytest.mark.parametrize("B,S,heads,masked", [(64, 185, 12, False), (3, 90, 12, True), (2, 281, 4, True), (1, 7, 1, False)])
+ATTN_CLS_SHAPES = [(64, 185, 12, False), (3, 90, 12, True), (2, 281, 4, True), (1, 7, 1, False)]
+
+
+@pytest.mark.parametrize("B,S,heads,masked", ATTN_CLS_SHAPES)
 def test_attention_token0_only_vs_dense_and_fp32(L, B, S, heads, masked):
     """feddat_attn_cls_fwd / _bwd (the last layer: one query per (sample, head)) against fp32 attention restricted to query 0,
     and against the dense kernels fed a dctx that is zero off token 0."""
@@ -742,8 +748,11 @@ def _attn_ref(qkv, B, S, heads, mask=None):
     return ctx, torch.logsumexp(sc, -1)
 
 
-@pytest.mark.parametrize("B,S,heads,masked", [(2, 185, 12, False), (3, 90, 12, True), (1, 33, 2, True),
-                                              (64, 185, 12, False), (2, 281, 12, True), (1, 320, 3, False)])
+ATTN_SHAPES = [(2, 185, 12, False), (3, 90, 12, True), (1, 33, 2, True), (64, 185, 12, False), (2, 281, 12, True),
+               (1, 320, 3, False)]
+
+
+@pytest.mark.parametrize("B,S,heads,masked", ATTN_SHAPES)
 def test_attention_fwd_bwd(L, B, S, heads, masked):
     g = torch.Generator().manual_seed(S)
     H = heads * 64
@@ -901,7 +910,10 @@ def test_adapter_fwd_with_fused_layernorm(L, golden_dir):
     assert ((y_a.float() - y_b.float()).abs() > 0).float().mean() < 0.02
 
 
-@pytest.mark.parametrize("M,N,K", [(64, 768, 3072), (64, 3072, 768), (8, 768, 768), (37, 768, 3072)])
+SKINNY_SHAPES = [(64, 768, 3072), (64, 3072, 768), (8, 768, 768), (37, 768, 3072)]
+
+
+@pytest.mark.parametrize("M,N,K", SKINNY_SHAPES)
 def test_gemm_skinny_all_epilogues(L, M, N, K):
     """Split-K skinny GEMM (top layer, 2B token-0 rows) against the same fp32 restatement as the big kernel, with a
     strided A operand and residual as the engine passes them."""
@@ -1014,7 +1026,7 @@ def test_fedavg_allreduce_through_the_c_abi_single_rank(L):
 
 
 # ------------------------------------------------------------------ K2b general attention (ALBEF path)
-@pytest.mark.parametrize("B,Sq,Skv,heads,causal,masked", [
+ATTN2_SHAPES = [
     (2, 577, 577, 12, False, False),     # ViT-B/16 at 384 x 384
     (3, 25, 577, 12, False, False),      # text -> image cross-attention
     (3, 25, 25, 12, False, True),        # text self-attention with padded questions
@@ -1028,7 +1040,10 @@ def test_fedavg_allreduce_through_the_c_abi_single_rank(L):
     (2, 128, 192, 2, False, False),      # whole chunks only: nothing is ever masked
     (2, 100, 100, 2, False, False),      # last chunk of 36 keys: forward on the masking kernel, backward mask-free
     (1, 70, 90, 2, False, False),        # last chunks of 26 keys / 6 queries
-])
+]
+
+
+@pytest.mark.parametrize("B,Sq,Skv,heads,causal,masked", ATTN2_SHAPES)
 def test_attn2_fwd_bwd_vs_fp32_reference(L, B, Sq, Skv, heads, causal, masked):
     g = torch.Generator().manual_seed(Sq * 1000 + Skv)
     H = heads * 64

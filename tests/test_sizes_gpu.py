@@ -269,8 +269,10 @@ def test_gemm_production_shapes_per_element(M, N, K):
     torch.cuda.synchronize()
 
 
-@pytest.mark.parametrize("M,N,K,fp8", [(11840, 3072, 768, False), (5920, 3072, 768, False), (1030, 192, 64, False),
-                                       (11840, 3072, 768, True)])
+GELU_CODE_SHAPES = [(11840, 3072, 768, False), (5920, 3072, 768, False), (1030, 192, 64, False), (11840, 3072, 768, True)]
+
+
+@pytest.mark.parametrize("M,N,K,fp8", GELU_CODE_SHAPES)
 def test_gemm_gelu_code_epilogues(M, N, K, fp8):
     """FEDDAT_EPI_GELU_G8 / FEDDAT_EPI_MUL_G8 (8-bit gelu' codes in place of the bf16 u).  Against the fp64 product:
       codes   within 1 of round((gelu'(u) - LO) / STEP) everywhere, equal on > 97 % (the packed-polynomial gelu' is within
