@@ -959,6 +959,8 @@ int prep_launch(const feddat_adapter_seg* segs, int nseg, int T, AdapterLaunch& 
         if (sg.row_begin < 0 || sg.row_end > T || sg.row_end < sg.row_begin) return FEDDAT_EINVAL;
         if (sg.row_begin + sg.x_row_delta < 0 || sg.row_end + sg.x_row_delta > T) return FEDDAT_EINVAL;
         if (sg.n_adapters != 1 && sg.n_adapters != 2) return FEDDAT_EINVAL;
+        // a train_slot past the segment's adapters matches no slot in the kernels: z_out / dz_out would receive zeros
+        if (bwd && (sg.train_slot < -1 || sg.train_slot >= sg.n_adapters)) return FEDDAT_EINVAL;
         for (int a = 0; a < sg.n_adapters; ++a) {
             if (!sg.wd[a] || !sg.wu[a] || !sg.bd[a] || !sg.bu[a]) return FEDDAT_EINVAL;
             if (bwd && (!sg.wdT[a] || !sg.wuT[a])) return FEDDAT_EINVAL;

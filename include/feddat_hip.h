@@ -238,11 +238,13 @@ int feddat_layernorm_bwd_dx_fp8(const void* dy_bf16, const float* dy_f32, long d
  *     out = x + sum_a scale[a] * (W_up[a] * relu(W_down[a] * x + b_down[a]) + b_up[a])
  * Weights are the bf16 operand copies written by feddat_adapter_pack (opaque layouts): wd, wu (+ wdT, wuT for the
  * backward); biases fp32.  H = 768, r = 48.
+ * Segments may be empty, need not start at row 0 and may leave rows between them: rows outside every segment are
+ * neither read (x rows: those of the segments shifted by x_row_delta) nor written.
  * ------------------------------------------------------------------------------------------- */
 typedef struct {
     int row_begin, row_end;
     int n_adapters;   /* 1 or 2 */
-    int train_slot;   /* backward: which adapter slot (0/1) gets weight grads, -1 = none */
+    int train_slot;   /* backward: which adapter slot (0 .. n_adapters - 1) gets weight grads, -1 = none; others: EINVAL */
     int x_row_delta;  /* input row = output row + x_row_delta (lets two segments share one input, layer 0) */
     int reserved;
     float scale[2];
