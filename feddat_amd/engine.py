@@ -36,6 +36,9 @@ class ViltDatEngine(LocalUpdateEngine):
     NPASS = 2
     # state-dict stems of the engine's adapters (adapter.py:22-58): slot a <-> "...output.adapter.<stem>{down,up}.{weight,bias}"
     ADAPTER_STEMS = ("adapter_0_", "adapter_1_", "adapter_2_")
+    # state-dict stem of the FFN's second product: Adaptered_ViltOutput keeps the HF ViltOutput as `.layer` (adaptered_output.py);
+    # an engine without adapters (vector_engine) reads the plain HF key
+    FFN2_STEM = "output.layer.dense."
 
     def __init__(self, params: Dict[str, torch.Tensor], tasks: Sequence[str], device, batch: int, res: int,
                  text_len: int = 40, layers: int = 12, num_labels: int = 100, lr: float = 1e-4,
@@ -149,7 +152,7 @@ class ViltDatEngine(LocalUpdateEngine):
             wqkv = torch.cat([wq, wk, wv], 0).contiguous()
             bqkv = torch.cat([P(Lp + f"attention.attention.{n}.bias") for n in ("query", "key", "value")]).contiguous()
             wo, w1, w2 = P(Lp + "attention.output.dense.weight"), P(Lp + "intermediate.dense.weight"), \
-                P(Lp + "output.layer.dense.weight")
+                P(Lp + self.FFN2_STEM + "weight")
             extra = {}
             if self.fp8:
                 extra["wqkv8"], extra["sqkv"] = fp8_of(wqkv)
@@ -169,7 +172,7 @@ class ViltDatEngine(LocalUpdateEngine):
                 extra, wqkv=bf16_of(wqkv), wqkvT=bf16_T(wqkv), bqkv=bqkv,
                 wo=bf16_of(wo), woT=bf16_T(wo), bo=P(Lp + "attention.output.dense.bias"),
                 w1=bf16_of(w1), w1T=bf16_T(w1), b1=P(Lp + "intermediate.dense.bias"),
-                w2=bf16_of(w2), w2T=bf16_T(w2), b2=P(Lp + "output.layer.dense.bias"),
+                w2=bf16_of(w2), w2T=bf16_T(w2), b2=P(Lp + self.FFN2_STEM + "bias"),
                 ln1g=P(Lp + "layernorm_before.weight"), ln1b=P(Lp + "layernorm_before.bias"),
                 ln2g=P(Lp + "layernorm_after.weight"), ln2b=P(Lp + "layernorm_after.bias")))
         self.lnf_g, self.lnf_b = P(ENC + "layernorm.weight"), P(ENC + "layernorm.bias")

@@ -54,6 +54,13 @@ class ViltLayerGrads(C.Structure):
     _fields_ = [(n, vp) for n in ("dh_out", "dh_in", "dh3", "dh16", "dU", "dx16", "dctx", "dqkv", "z", "dz")]
 
 
+class VgradJob(C.Structure):         # feddat_vgrad_job
+    _fields_ = [("partials", vp), ("grad", vp), ("slabs", i32), ("n", i32), ("flags", i32), ("reserved", i32)]
+
+
+VGRAD_UNSCALED = 1
+
+
 class HtJob(C.Structure):            # feddat_ht_job
     _fields_ = [("A", vp), ("sa_i", i64), ("sa_k", i64), ("B", vp), ("sb_k", i64), ("sb_j", i64), ("I", i32), ("J", i32),
                 ("K", i32), ("mode", i32), ("alpha", f32), ("bias_j", vp), ("out", vp), ("ldo", i64), ("colsum", vp),
@@ -144,6 +151,10 @@ _SIGS = {
     "feddat_dat_step_finish": [vp, vp, vp, vp, vp, vp, f32, f32, i32, vp],
     "feddat_bce_loss_fwd_bwd": [vp, vp, i32, i32, vp, vp, vp, vp],
     "feddat_single_step_finish": [C.POINTER(vp), i32, vp, vp, vp, f32, f32, i32, vp],
+    "feddat_vector_grad_workspace_elems": [i32, i32],
+    "feddat_colsum_partial": [vp, vp, i64, vp, i32, i32, vp, i64, vp],
+    "feddat_ln_param_grad_partial": [vp, vp, i64, vp, i64, vp, i32, i32, vp, vp, i64, vp],
+    "feddat_vector_grad_reduce": [vp, i32, i32, f32, vp, vp, vp],
     "feddat_head_gemm": [C.POINTER(HtJob), i32, vp],
     "feddat_head_ln_gelu": [vp, vp, vp, f32, i32, i32, vp, vp, vp, vp],
     "feddat_head_ln_bwd_full": [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp],
@@ -747,6 +758,78 @@ def bce_loss_fwd_bwd(logits, target, dlogits, scalars, nonfinite=None):
     assert scalars.numel() >= 1 and (nonfinite is None or nonfinite.dtype == torch.int32)
     _chk(load().feddat_bce_loss_fwd_bwd(_p(logits), _p(target), B, Cn, _p(dlogits), _p(scalars),
                                         _p(nonfinite), _stream()), "feddat_bce_loss_fwd_bwd")
+
+
+# ---- gradients of per-column vectors (optimizer_mode bias / norm; include/feddat_hip.h, csrc/vector_grad.hip)
+def vector_grad_workspace_elems(rows: int, N: int) -> int:
+    """Floats of one partial buffer for `rows` rows of N columns (slabs * N)."""
+    return int(load().feddat_vector_grad_workspace_elems(int(rows), int(N)))
+
+
+def _rows_of(t, what):
+    """(16-bit pointer, fp32 pointer, row stride) of a [rows, N] matrix whose rows are contiguous."""
+    if t.dim() != 2 or t.stride(1) != 1:
+        raise FeddatHipError(f"{what} must be a [rows, N] matrix with contiguous rows")
+    if t.dtype == torch.float32:
+        return None, _p(t), t.stride(0)
+    if t.dtype != OPERAND_DTYPE[current_operands()]:
+        raise FeddatHipError(f"{what} must be fp32 or the bound library's operand format, got {t.dtype}")
+    return _p(t), None, t.stride(0)
+
+
+def colsum_partial(x, partials, row_mask=None):
+    """partials[s] = sum of the rows of slab s of x [rows, N] (16-bit operands or fp32; row stride = x.stride(0)); row_mask:
+    optional uint8 [rows], rows with 0 are left out.  Returns the number of slabs written."""
+    _dev(x, partials, row_mask)
+    p16, p32, ld = _rows_of(x, "x")
+    rows, N = x.shape
+    assert partials.dtype == torch.float32 and partials.is_contiguous()
+    assert row_mask is None or (row_mask.dtype == torch.uint8 and row_mask.numel() == rows and row_mask.is_contiguous())
+    _chk(load().feddat_colsum_partial(p16, p32, ld, _p(row_mask), rows, N, _p(partials), partials.numel(), _stream()),
+         "feddat_colsum_partial")
+    return vector_grad_workspace_elems(rows, N) // N
+
+
+def ln_param_grad_partial(dy, x, stats, dbeta_partials, dgamma_partials=None):
+    """One pass over the rows of a LayerNorm: dbeta_partials[s] = sum dy, dgamma_partials[s] = sum dy * xhat (None: beta
+    alone, x and stats are not read).  dy 16-bit operands or fp32, x fp32, stats the saved {mean, rstd} rows."""
+    _dev(dy, x, stats, dbeta_partials, dgamma_partials)
+    p16, p32, ld = _rows_of(dy, "dy")
+    rows, N = dy.shape
+    n = dbeta_partials.numel()
+    assert dbeta_partials.dtype == torch.float32 and dbeta_partials.is_contiguous()
+    xs = 0
+    if dgamma_partials is not None:
+        assert dgamma_partials.dtype == torch.float32 and dgamma_partials.is_contiguous() and dgamma_partials.numel() >= n
+        assert x.dtype == torch.float32 and x.stride(1) == 1 and x.shape[0] >= rows and stats.dtype == torch.float32
+        assert stats.is_contiguous() and stats.numel() >= 2 * rows
+        xs = x.stride(0)
+    _chk(load().feddat_ln_param_grad_partial(p16, p32, ld, _p(x), xs, _p(stats), rows, N, _p(dgamma_partials),
+                                             _p(dbeta_partials), n, _stream()), "feddat_ln_param_grad_partial")
+    return vector_grad_workspace_elems(rows, N) // N
+
+
+def make_vgrad_jobs(jobs, device):
+    """Device-resident feddat_vgrad_job table from [(partials, slabs, grad[, flags])] (grad: the N-float slice of a flat
+    gradient buffer the job writes; flags: VGRAD_UNSCALED).  Returns (table, njobs, max_n); the caller keeps the tensors alive."""
+    arr = (VgradJob * len(jobs))()
+    for j, (part, slabs, grad, *fl) in zip(arr, jobs):
+        j.flags = fl[0] if fl else 0
+        _dev(part, grad)
+        assert part.dtype == torch.float32 and grad.dtype == torch.float32 and grad.is_contiguous()
+        assert part.numel() >= slabs * grad.numel()
+        j.partials, j.grad, j.slabs, j.n = part.data_ptr(), grad.data_ptr(), int(slabs), grad.numel()
+    table = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(device)
+    return table, len(jobs), max(job[2].numel() for job in jobs)
+
+
+def vector_grad_reduce(table, njobs, max_n, unscale=1.0, unscale_dev=None, nonfinite=None):
+    """Fold every job's partials into its gradient slice, times unscale * unscale_dev[0]; nonfinite (int32 device tensor,
+    optional) gets 1 OR-ed in on an inf / NaN (include/feddat_hip.h: feddat_vector_grad_reduce)."""
+    _dev(table, unscale_dev, nonfinite)
+    assert nonfinite is None or nonfinite.dtype == torch.int32
+    _chk(load().feddat_vector_grad_reduce(_p(table), njobs, max_n, unscale, _p(unscale_dev), _p(nonfinite), _stream()),
+         "feddat_vector_grad_reduce")
 
 
 def single_step_finish(states, flag, scaler_f, scaler_i, growth=2.0, backoff=0.5, growth_interval=2000):

@@ -1,5 +1,5 @@
 """Host-side protocol that every local-update engine shares around its HIP step (ViltDatEngine, ViltAdapterEngine,
-AlbefDatEngine): the flat trainable groups, the device-side loss scaler (GradScaler on the device), the
+ViltVectorEngine, AlbefDatEngine): the flat trainable groups, the device-side loss scaler (GradScaler on the device), the
 AdamW launches and the DAT optimizer tail, the start of a local update, hipGraph capture, and the trainable state.
 
 An engine derived from LocalUpdateEngine supplies its step (`_step_kernels`), its adapters (`ad`, `repack_adapter`), the

@@ -18,7 +18,7 @@ import torch
 
 from . import lib as L
 from .engine import ViltDatEngine, ENC
-from .modes import mode_names
+from .modes import MODES, VECTOR_MODES, mode_names
 
 
 class _Param:
@@ -201,7 +201,9 @@ class ViltContinualLearner:
         """operands: 16-bit MFMA operand format of the engine, "f16" (default; the reference's mixed_precision: fp16,
         accelerate_config.yaml:8) or "bf16" (engine.ViltDatEngine).
         optimizer_mode: "dat" (adapter_{0,1,2}, engine.ViltDatEngine) or "adapter" (the FedAvg baseline: one adapter per
-        layer, adapter_engine.ViltAdapterEngine; main.py:114-118,141-149)."""
+        layer, adapter_engine.ViltAdapterEngine; main.py:114-118,141-149), "bias" or "norm" (the plain backbone with every
+        'bias' / 'norm' parameter trainable, vector_engine.ViltVectorEngine; main.py:176-196).  state_dict() holds the trainable
+        tensors under the reference's keys; bias / norm add no parameters."""
         self.ordered_cl_tasks = list(ordered_cl_tasks)
         self.device = torch.device(device)
         self.optimizer_mode = optimizer_mode
@@ -210,8 +212,12 @@ class ViltContinualLearner:
             Engine = ViltAdapterEngine
         elif optimizer_mode == "dat":
             Engine = ViltDatEngine
+        elif optimizer_mode in VECTOR_MODES:
+            import functools
+            from .vector_engine import ViltVectorEngine
+            Engine = functools.partial(ViltVectorEngine, mode=optimizer_mode)
         else:
-            raise L.FeddatHipError(f"optimizer_mode must be 'dat' or 'adapter', got {optimizer_mode!r}")
+            raise L.FeddatHipError(f"optimizer_mode must be one of {MODES}, got {optimizer_mode!r}")
         self.engine = Engine(params, self.ordered_cl_tasks, self.device, batch=batch_size, res=image_size, layers=num_layers,
                              lr=lr, operands=operands)
         self.max_text_length = self.engine.Lt               # vilt.py:50: config.max_position_embeddings = 40
@@ -219,16 +225,19 @@ class ViltContinualLearner:
         self._tokenizer = None
         self._image_processor = None
         self.gating = False
-        self.active = "adapter_1" if optimizer_mode == "dat" else "adapter"
+        self.active = "adapter_1" if optimizer_mode == "dat" else "adapter" if optimizer_mode == "adapter" else None
         # requires_grad flags per adapter, toggled exactly like adapter.py:66-95; prepare_model's initial state
         # (main.py:157-159 + adapter.py:55-58): adapter_0/1 trainable, adapter_2 frozen.  The single adapter is always
         # trainable (set_active_adapter('adapter') flips no flag)
-        self.adapter_requires_grad = {0: True, 1: True, 2: False} if optimizer_mode == "dat" else {0: True}
-        # main.py:141-149,160-163: adapter_1 (dat) / every adapter key (adapter)
+        self.adapter_requires_grad = {0: True, 1: True, 2: False} if optimizer_mode == "dat" else \
+            {0: True} if optimizer_mode == "adapter" else {}
+        # main.py:141-149,160-163,176-196: adapter_1 (dat) / every adapter key (adapter) / every 'bias' resp. 'norm' key
         self.comm_state_dict_names = mode_names(list(self.state_dict()), optimizer_mode)["communicated"]
 
     # ---- adapter switches (vilt.py:363-373) ----
     def set_active_adapter(self, name):
+        if self.optimizer_mode in VECTOR_MODES:
+            raise L.FeddatHipError(f"optimizer_mode {self.optimizer_mode} has no adapter (got {name!r})")
         if self.optimizer_mode == "adapter":
             if name != "adapter":
                 raise L.FeddatHipError(f"optimizer_mode adapter has one adapter, 'adapter' (got {name!r})")
@@ -249,6 +258,8 @@ class ViltContinualLearner:
         """Which adapters a freshly created optimizer would hold (create_optimizer filters on requires_grad)."""
         if self.optimizer_mode == "adapter":
             return (0,)
+        if self.optimizer_mode in VECTOR_MODES:      # no adapter: the optimizer holds the mode's vectors and the head
+            return ()
         return tuple(a for a in (0, 1) if self.adapter_requires_grad[a])
 
     # ---- state dict with the reference's keys ----
@@ -308,7 +319,7 @@ class ViltContinualLearner:
     def forward(self, task_key: str, images, texts=None):
         if not isinstance(images, dict):
             images = self.process_inputs(images, texts)
-        if self.optimizer_mode == "adapter":
+        if self.optimizer_mode == "adapter" or self.optimizer_mode in VECTOR_MODES:
             return self.engine.forward(images, task_key)
         mode = "gating" if self.gating else self.active
         return self.engine.forward(images, mode, task_key)

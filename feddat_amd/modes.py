@@ -1,9 +1,30 @@
 """Which state-dict tensors train, travel to the server and stay with the client, per optimizer_mode (src/train/main.py:
-114-118,141-163,248-250 and the personal-parameter shuttle of main.py:440-450,473-497).
+114-118,141-163,176-196,246-250 and the personal-parameter shuttle of main.py:440-450,467-497).  The reference matches by
+case-sensitive SUBSTRING, over named_parameters() for "trainable" and over state_dict() keys for "communicated", and this
+module does the same on the keys it is given.
 
   mode       trainable                      communicated (FedAvg)     personal (kept per client)
   dat        adapter_0, adapter_1, heads    adapter_1                 heads, adapter_0, adapter_2
   adapter    adapter, heads                 every 'adapter' key       heads ('task')
+  bias       every 'bias' key, heads        every 'bias' key          heads ('task')
+  norm       every 'norm' key, heads        every 'norm' key          heads ('task')
+
+bias (BitFit): per layer query|key|value.bias, attention.output.dense.bias, intermediate.dense.bias, output.dense.bias (the HF key: no Adaptered_ViltOutput here),
+layernorm_before.bias, layernorm_after.bias (8 448 floats), once text_embeddings.LayerNorm.bias,
+patch_embeddings.projection.bias, layernorm.bias, pooler.dense.bias: 104 448 backbone floats at 12 layers.
+norm: layernorm_before.{weight,bias}, layernorm_after.{weight,bias}, vilt.layernorm.{weight,bias} (38 400 floats).
+text_embeddings.LayerNorm.* does NOT match 'norm' (capital N) and stays frozen.
+
+Tensors that are BOTH communicated and personal: the heads' own matches -- task_layer.<t>.clf_fc0.bias, clf_norm0.bias and
+clf_fc1.bias in bias mode; task_layer.<t>.clf_norm0.weight and clf_norm0.bias in norm mode (the head's LayerNorm is named
+clf_norm0: vilt.py:202-209).  They sit in the server's comm_state_dict_names, but get_average_net skips every key that
+contains 'clf' (main.py:54), and each client overwrites them with its personal copy before it trains (main.py:467-474):
+the server's copies never move, the clients' never mix.  averaged_names() is the communicated list minus those keys, i.e.
+what actually changes on the server.
+
+Weight decay follows task_trainer.py:477-504 (local_update._no_decay): a name containing 'bias' or 'LayerNorm.weight' is
+not decayed.  layernorm_{before,after}.weight and vilt.layernorm.weight contain neither, so the gammas of norm mode ARE
+decayed; every bias is not.
 """
 from __future__ import annotations
 
@@ -11,7 +32,9 @@ from typing import Dict, List, Sequence
 
 from . import lib as L
 
-MODES = ("dat", "adapter")
+MODES = ("dat", "adapter", "bias", "norm")
+# the modes whose trainable backbone tensors are per-column vectors (vector_engine.ViltVectorEngine)
+VECTOR_MODES = ("bias", "norm")
 
 
 def mode_names(keys: Sequence[str], mode: str) -> Dict[str, List[str]]:
@@ -23,6 +46,12 @@ def mode_names(keys: Sequence[str], mode: str) -> Dict[str, List[str]]:
         return dict(trainable=[k for k in keys if "task" in k or "adapter_0" in k or "adapter_1" in k],
                     communicated=[k for k in keys if "adapter_1" in k],
                     personal=[k for k in keys if "task" in k or "adapter_0" in k or "adapter_2" in k])
-    return dict(trainable=[k for k in keys if "adapter" in k or "task" in k],
-                communicated=[k for k in keys if "adapter" in k],
+    sub = mode          # "adapter" | "bias" | "norm": the substring main.py matches is the mode's own name
+    return dict(trainable=[k for k in keys if sub in k or "task" in k],
+                communicated=[k for k in keys if sub in k],
                 personal=[k for k in keys if "task" in k])
+
+
+def averaged_names(keys: Sequence[str], mode: str) -> List[str]:
+    """The communicated keys the server really averages: get_average_net leaves out every key containing 'clf' (main.py:54)."""
+    return [k for k in mode_names(keys, mode)["communicated"] if "clf" not in k]

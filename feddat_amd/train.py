@@ -26,7 +26,7 @@ from . import lib as L
 from . import vilt_spec
 from .fedavg import all_reduce_sum, allreduce_average, get_average_net  # noqa: F401  (re-exported: main.py:50)
 from .modeling import ViltContinualLearner, convert_batch_to_vilt_input_dict, create_vilt_continual_learner_model
-from .modes import mode_names
+from .modes import MODES, VECTOR_MODES, mode_names
 
 
 class OptimizerHandle:
@@ -160,9 +160,9 @@ class TaskTrainer:
         switches the reference performs inside (activate_gating / set_active_adapter, task_trainer.py:284-312)
         leave the model in the same final state: gating on, adapter_0 active.
         optimizer_mode adapter: one forward / backward / AdamW step / scheduler tick (task_trainer.py:433-450); returns
-        loss = BCE * num_labels."""
+        loss = BCE * num_labels.  optimizer_mode bias / norm: the same step on the adapter-less model."""
         out = model.engine.train_step(self.encode_batch(model, batch), use_graph=self.use_graph)
-        if self._mode(model) == "adapter":
+        if self._mode(model) == "adapter" or self._mode(model) in VECTOR_MODES:
             return out[0]
         model.activate_gating()
         model.set_active_adapter("adapter_0")
@@ -183,6 +183,8 @@ class TaskTrainer:
 
     def eval(self, model: ViltContinualLearner):
         loader = self.vqa_test_dataloader
+        if self._mode(model) in VECTOR_MODES:      # no adapter to switch: one score
+            return self.eval_one_loader(model, loader)
         if self._mode(model) == "adapter":      # task_trainer.py:232-233,246: one score
             model.set_active_adapter("adapter")
             return self.eval_one_loader(model, loader)
@@ -358,10 +360,11 @@ TASK_SETS = {   # main.py:352-359
 def main(argv=None):
     args = build_parser().parse_args(argv)
     mode = "dat" if "dat" in args.optimizer_mode else args.optimizer_mode
-    if mode not in ("dat", "adapter"):
-        raise L.FeddatHipError("--optimizer_mode dat or adapter are on the MI355X hot path (SURVEY.md section 2, row 13)")
-    if mode == "adapter" and "albef" in args.encoder_name:
-        raise L.FeddatHipError("ALBEF supports only --optimizer_mode dat (adapter is a ViLT mode here)")
+    if mode not in MODES:
+        raise L.FeddatHipError("--optimizer_mode dat, adapter, bias or norm are on the MI355X hot path (SURVEY.md section 2, "
+                               "row 13)")
+    if mode != "dat" and "albef" in args.encoder_name:
+        raise L.FeddatHipError("ALBEF supports only --optimizer_mode dat (adapter, bias and norm are ViLT modes here)")
     logging.basicConfig(level=logging.INFO, format="%(asctime)s - %(levelname)s - %(message)s")
     log = logging.getLogger("feddat_amd")
     if args.mixed_precision is None:       # one default, the same as bench.py's and the engines' own
@@ -428,7 +431,7 @@ def main(argv=None):
                                                     optimizer_mode=mode)
         Trainer = TaskTrainer
     eng = model.engine
-    # personal parameters per client (main.py:440-450): head + adapter_0 + adapter_2 (dat) / head (adapter)
+    # personal parameters per client (main.py:440-450): head + adapter_0 + adapter_2 (dat) / head (adapter, bias, norm)
     def personal(sd):
         keep = set(mode_names(list(sd), mode)["personal"])
         return {n: v.clone() for n, v in sd.items() if n in keep}

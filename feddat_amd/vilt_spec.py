@@ -14,9 +14,10 @@ ENC = "vilt_encoder.vilt."
 def param_shapes(layers: int = 12, tasks: Sequence[str] = ("art",), hidden: int = 768, inter: int = 3072,
                  patch: int = 32, grid: int = 12, max_text: int = 40, vocab: int = 30522, num_labels: int = 100,
                  bottleneck: int = 48, optimizer_mode: str = "dat") -> Dict[str, Tuple[int, ...]]:
-    """optimizer_mode "dat": adapter_{0,1,2} in every layer; "adapter": the single `adapter` (main.py:114-118)."""
+    """optimizer_mode "dat": adapter_{0,1,2} in every layer; "adapter": the single `adapter` (main.py:114-118); "bias" / "norm":
+    the plain backbone, no adapter (these modes add no parameters)."""
     H, I, r = hidden, inter, bottleneck
-    stems = {"dat": ("adapter_0_", "adapter_1_", "adapter_2_"), "adapter": ("adapter_",)}[optimizer_mode]
+    stems = {"dat": ("adapter_0_", "adapter_1_", "adapter_2_"), "adapter": ("adapter_",), "bias": (), "norm": ()}[optimizer_mode]
     s: Dict[str, Tuple[int, ...]] = {}
     e = ENC + "embeddings."
     s[e + "cls_token"] = (1, 1, H)
@@ -38,8 +39,10 @@ def param_shapes(layers: int = 12, tasks: Sequence[str] = ("art",), hidden: int 
         s[L + "attention.output.dense.bias"] = (H,)
         s[L + "intermediate.dense.weight"] = (I, H)
         s[L + "intermediate.dense.bias"] = (I,)
-        s[L + "output.layer.dense.weight"] = (H, I)
-        s[L + "output.layer.dense.bias"] = (H,)
+        # Adaptered_ViltOutput keeps the HF ViltOutput as `.layer`; without an adapter (bias / norm) the HF keys stay as they are
+        out = "output.layer.dense." if stems else "output.dense."
+        s[L + out + "weight"] = (H, I)
+        s[L + out + "bias"] = (H,)
         for stem in stems:
             A = L + f"output.adapter.{stem}"
             s[A + "down.weight"] = (r, H)

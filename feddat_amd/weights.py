@@ -151,8 +151,10 @@ def convert_vilt_state_dict(sd: Dict[str, torch.Tensor], layers: int = 12) -> Di
 def load_vilt_pretrained(path: str, tasks: Sequence[str], layers: int = 12, seed: int = 0,
                          num_labels: int = 100, optimizer_mode: str = "dat") -> Dict[str, torch.Tensor]:
     """Everything create_vilt_continual_learner_model needs: frozen backbone from `path`, fresh adapters (adapter_{0,1,2}, or
-    the single `adapter` with optimizer_mode "adapter") and heads."""
+    the single `adapter` with optimizer_mode "adapter", none with "bias" / "norm") and heads."""
     sd = convert_vilt_state_dict(read_checkpoint(path), layers)
+    if optimizer_mode in ("bias", "norm"):      # no Adaptered_ViltOutput: the FFN's second product keeps its HF key
+        sd = {k.replace(".output.layer.dense.", ".output.dense."): v for k, v in sd.items()}
     shapes = vilt_spec.param_shapes(layers, tasks, num_labels=num_labels, optimizer_mode=optimizer_mode)
     for k, shp in shapes.items():
         if k in sd and tuple(sd[k].shape) != tuple(shp):

@@ -498,6 +498,39 @@ int feddat_bce_loss_fwd_bwd(const float* logits, const float* target, int B, int
 int feddat_single_step_finish(int* const* states, int n, int* flag, float* scaler_f, int* scaler_i, float growth,
                               float backoff, int growth_interval, hipStream_t stream);
 
+/* Gradients of per-column vectors over a long row dimension (optimizer_mode bias / norm: a linear layer's bias, a LayerNorm's
+ * gamma and beta over R = B * S rows) -- additions within ABI 8 (csrc/vector_grad.hip).  Two stages, both with a summation order
+ * that depends on (rows, N) only and no floating-point atomics, so equal inputs give equal bits:
+ * feddat_vector_grad_workspace_elems(rows, N): floats one partial buffer needs = slabs * N, slabs = ceil(rows / 64).
+ * feddat_colsum_partial: partials[s, c] = sum over the rows r of slab s (with row_mask[r] != 0 when row_mask, DEVICE bytes
+ *   [rows], is given) of x[r * x_stride + c]; x is [rows, N] of 16-bit operands (x_bf16, the build's format) or fp32 (x_f32),
+ *   exactly one of the two; N % 8 == 0, x_stride % 8 == 0, x_stride >= N, 16-byte aligned base; fp32 accumulation.
+ * feddat_ln_param_grad_partial: for y = xhat * gamma + beta with xhat = (x - mean) * rstd, stats[r] = {mean, rstd} as
+ *   feddat_layernorm_fwd saves them: dbeta_partials[s, c] = sum_r dy[r, c] and dgamma_partials[s, c] = sum_r dy[r, c] * xhat[r, c]
+ *   in ONE pass over the rows; dy 16-bit or fp32 (exactly one), x fp32 with x_stride % 4 == 0.  dgamma_partials may be NULL (beta
+ *   alone: x and stats are then not read and may be NULL).  Both partial buffers hold partials_elems floats.
+ * feddat_vector_grad_reduce: ONE launch for every vector of a step.  jobs_dev is a DEVICE array of njobs descriptors; job j
+ *   writes grad[c] = (sum over its slabs of partials[s * n + c]) * unscale * (*unscale_dev when given: 1 / the dynamic loss
+ *   scale) for c < n <= max_n, and *nonfinite (DEVICE int, may be NULL) is OR-ed with 1 when any written value is inf / NaN
+ *   (GradScaler's inf check, as feddat_adapter_wgrad_reduce_checked does for the adapters).  unscale 0 = 1. */
+typedef struct feddat_vgrad_job {
+    const float* partials;   /* [slabs, n] fp32, written by one of the partial entry points */
+    float* grad;             /* n floats of a flat gradient buffer */
+    int slabs;
+    int n;
+    int flags;               /* FEDDAT_VGRAD_UNSCALED: the sum is written as it is (neither unscale nor *unscale_dev applied) */
+    int reserved;
+} feddat_vgrad_job;
+#define FEDDAT_VGRAD_UNSCALED 1
+long feddat_vector_grad_workspace_elems(int rows, int N);
+int feddat_colsum_partial(const void* x_bf16, const float* x_f32, long x_stride, const unsigned char* row_mask, int rows,
+                          int N, float* partials, long partials_elems, hipStream_t stream);
+int feddat_ln_param_grad_partial(const void* dy_bf16, const float* dy_f32, long dy_stride, const float* x, long x_stride,
+                                 const float* stats, int rows, int N, float* dgamma_partials, float* dbeta_partials,
+                                 long partials_elems, hipStream_t stream);
+int feddat_vector_grad_reduce(const feddat_vgrad_job* jobs_dev, int njobs, int max_n, float unscale,
+                              const float* unscale_dev, int* nonfinite, hipStream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * K5  loss.  L = (BCEWithLogits_mean(logits,target) * C + 9 * KL_batchmean(log_softmax(logits/3) ||
  * softmax(teacher/3))) / 2   (task_trainer.py:299-301,506-516; train_vqa_crossvqa.py:237).
