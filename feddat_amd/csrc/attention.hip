@@ -632,6 +632,8 @@ extern "C" int feddat_attn_bwd(const void* qkv, const uint8_t* key_mask, const v
                                const void* dctx, void* dqkv, int B, int S, int heads, hipStream_t stream) {
     FD_CHECK_ARG(qkv && ctx && lse && dctx && dqkv && B > 0 && S > 0 && S <= 320 && heads > 0);
     const int nks = (S + 31) / 32;
+    // debug flag 2: the two-role kernel also at S <= 192.  Its role 0 repeats the fused kernel's phase A operation for operation
+    // (dK | dV bit-identical); its role 1 recomputes dQ with its own D = sum_d dO O (another summation order): not bit-identical.
     if (nks <= 6 && !(fd_debug_flags() & 2)) {        // one block per (sample, head): operands and probabilities once
         const int sp = nks * 32;
         const int ldsf = 3 * sp * ROWB + sp * sp * 2 + 3 * sp * 4;

@@ -58,10 +58,12 @@ int fd_set_max_lds(const void* kernel, int bytes);     // hipFuncAttributeMaxDyn
 // only in the -DFEDDAT_ABLATE build (`python -m feddat_amd.build --ablate` -> libfeddat_hip_ablate.so, loaded explicitly by
 // tools/ through lib.use_ablation_build()).  The production library compiles them out: FD_ABL(x) is the constant 0 there, and
 // feddat_set_debug_flags rejects every bit outside FD_DEBUG_SELECT_BITS, which only choose among kernels that give the same
-// (bit-identical) results: 1 / 2 everything on the two-group / one-wave-per-SIMD GEMM kernel (2 in attention.hip: the
-// two-role backward), 1 | 2 together the DUAL form of the persistent GEMM (two independent 128 x 192 workgroups per CU; with 64:
+// (bit-identical) results -- with ONE exception, flag 2 in attention.hip -- : 1 / 2 everything on the two-group /
+// one-wave-per-SIMD GEMM kernel (2 in attention.hip: the two-role backward at S <= 192, whose dK | dV are bit-identical with the
+// fused kernel's and whose dQ is NOT: role 1 recomputes the scores in the transposed orientation and sums D = sum_d dO O in another
+// order; equally accurate, tests/test_attention_kernels_gpu.py holds both to the same per-element bound), 1 | 2 together the DUAL form of the persistent GEMM (two independent 128 x 192 workgroups per CU; with 64:
 // only where it has at least two rounds of tiles), 32 / 64 force 192- / 256-row tiles, 128 no small-tile kernel, 256 the K = 32 fp8 MFMA, bit 23 one
-// attention-backward block per pair, bit 27 no 160-row GEMM tiles, bits 28..31 cap the persistent GEMM grid at 16 x value workgroups.
+// attention-backward block per pair (the same kernel as the persistent grid: bit-identical for every pair count, ragged last round included), bit 27 no 160-row GEMM tiles, bits 28..31 cap the persistent GEMM grid at 16 x value workgroups.
 #ifdef FEDDAT_ABLATE
 #define FD_ABL(x) (x)
 #else

@@ -267,7 +267,8 @@ def use_ablation_build():
 
 
 def set_debug_flags(flags: int):
-    """Kernel-selection switches (bit-identical results): 1 / 2 GEMMs on the two-group / one-wave-per-SIMD kernel, 32 / 64
+    """Kernel-selection switches (bit-identical results, except dQ of the two-role attention backward that flag 2 selects at
+    S <= 192: equally accurate, not bit-identical; its dK | dV are): 1 / 2 GEMMs on the two-group / one-wave-per-SIMD kernel, 32 / 64
     force 192- / 256-row tiles, 128 no small-tile kernel, 256 K = 32 fp8 MFMA, bit 23 one attention-backward block per pair,
     bits 28..31 cap the persistent GEMM grid.  The timing-only ablations (8 skip epilogue, 4 / 16, 512, bits 8..22, 24..26)
     exist in the ablation build only (use_ablation_build)."""

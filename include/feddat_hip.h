@@ -55,7 +55,8 @@ int feddat_operand_format(void);   /* which 16-bit format this library's "bf16" 
  * feddat_set_debug_flags: ablation switches used by tools/ only (GEMM: 1 / 2 = everything on the two-wave-group / the
  * one-wave-per-SIMD kernel, 8 = skip epilogue, 32 / 64 = force 192- / 256-row tiles, 256 = K = 32 fp8 MFMA, 512 = deferred-
  * epilogue timing probe, bits 28..31 = cap the persistent grid at 16 x value workgroups; adapters: bits 24..26; attention
- * backward: bits 20..22 = timing-only ablations, bit 23 = one block per (sample, head) instead of the persistent grid).  The one piece
+ * backward: bits 20..22 = timing-only ablations, bit 23 = one block per (sample, head) instead of the persistent grid, bit-identical;
+ * 2 = the two-role kernel also at S <= 192: dK | dV bit-identical with the default, dQ equally accurate but not bit-identical).  The one piece
  * of process-wide mutable state in the library: 0 by default, never read from the environment, and no production path sets
  * it -- with flags = 0 every launch is a pure function of its arguments.
  * ------------------------------------------------------------------------------------------- */
@@ -153,6 +154,20 @@ int feddat_gemm_bf16_nt_skinny(const void* A, int lda, const void* B, int ldb, i
  * key_mask: optional uint8 [B,S] (1 = attend, 0 = masked; text padding, vilt.py:98) or NULL.
  * ctx: bf16 [B*S, H]; lse: fp32 [B, heads, S] (log-sum-exp of the scaled scores, saved for backward).
  * Requirements: head_dim == 64, S <= 320 (ViLT: 40 text + 1 + up to 12 x 20 patches of a 384 x 640 image = 281).
+ * The key mask, for every attention entry point of this header (K2 and the general form below):
+ *  - any NON-ZERO byte attends; the results are bit-identical with those for the byte 1.
+ *  - every query must be left at least one key (mask, causal and sequence end together).  A sample whose keys are all masked is
+ *    OUTSIDE THE CONTRACT of feddat_attn_fwd / _bwd / _cls_fwd / _cls_bwd (they divide by a zero sum: NaN in that sample's rows;
+ *    the reference's additive -10000 would give a uniform softmax instead) and of every backward.  feddat_attn2_fwd defines it:
+ *    ctx = 0 and lse = -inf for such a query -- an lse that no backward accepts (0 x exp2(+inf)).  Either way the other samples of
+ *    the launch are not disturbed.
+ *  - dK and dV rows of masked keys are exact zeros, and the K / V rows of masked keys reach no result (ctx, lse and every other
+ *    gradient row are bit-identical whatever finite values they hold), with one limit in the backward kernels: they form
+ *    valid * exp2(score - lse), masking AFTER the exponential, so a masked key whose score exceeds its row's lse by more than
+ *    fp32's exponent range (128 in the log2 domain, i.e. q . k / 8 - lse > 88) gives 0 x inf = NaN.  Activations of ordinary
+ *    magnitude stay far from it (the forward masks before the exponential and has no such limit); the token-0 backward
+ *    (feddat_attn_cls_bwd) masks before the exponential.
+ * Checked element by element against float64 in both operand builds by tests/test_attention_kernels_gpu.py.
  * ------------------------------------------------------------------------------------------- */
 int feddat_attn_fwd(const void* qkv, const uint8_t* key_mask, void* ctx, float* lse, int B, int S, int heads,
                     hipStream_t stream);
