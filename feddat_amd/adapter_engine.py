@@ -104,7 +104,3 @@ class ViltAdapterEngine(ViltDatEngine):
     def forward(self, batch: Dict[str, torch.Tensor], task: Optional[str] = None):
         """model(task_key, images, texts) -> (pooled, logits) with set_active_adapter('adapter') (vilt.py:244-264)."""
         return super().forward(batch, "adapter", task)
-
-    def repack(self):
-        """fp32 master adapter -> 16-bit MFMA operand copies (after a load / FedAvg write-back)."""
-        self.repack_adapter(0)

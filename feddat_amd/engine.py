@@ -17,27 +17,23 @@ Restructuring relative to the reference (same results, fewer FLOPs -- DESIGN.md 
 """
 from __future__ import annotations
 
-import math
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, Optional, Sequence, Tuple
 
 import torch
 
 from . import lib as L
-from .local_update import FlatGroup, LocalUpdateEngine, _bound
+from .local_update import FlatGroup, _bound
+from .vilt_backbone import ENC, HEAD_TENSORS, ViltBackbone  # noqa: F401 -- ENC / HEAD_TENSORS are imported from here
 
-ENC = "vilt_encoder.vilt."
 ADAPTER_TENSORS = ("down.weight", "down.bias", "up.weight", "up.bias")
-HEAD_TENSORS = ("clf_fc0.weight", "clf_fc0.bias", "clf_norm0.weight", "clf_norm0.bias", "clf_fc1.weight",
-                "clf_fc1.bias")
 
 
-class ViltDatEngine(LocalUpdateEngine):
+class ViltDatEngine(ViltBackbone):
     # passes per sample through the backbone: the DAT step runs the gated and the adapter_1 pass as one batch of 2 B samples
     NPASS = 2
     # state-dict stems of the engine's adapters (adapter.py:22-58): slot a <-> "...output.adapter.<stem>{down,up}.{weight,bias}"
     ADAPTER_STEMS = ("adapter_0_", "adapter_1_", "adapter_2_")
-    # state-dict stem of the FFN's second product: Adaptered_ViltOutput keeps the HF ViltOutput as `.layer` (adaptered_output.py);
-    # an engine without adapters (vector_engine) reads the plain HF key
+    # state-dict stem of the FFN's second product: Adaptered_ViltOutput keeps the HF ViltOutput as `.layer` (adaptered_output.py)
     FFN2_STEM = "output.layer.dense."
 
     def __init__(self, params: Dict[str, torch.Tensor], tasks: Sequence[str], device, batch: int, res: int,
@@ -76,29 +72,19 @@ class ViltDatEngine(LocalUpdateEngine):
         operands = operands or ("bf16" if fp8 else "f16")
         if fp8 and operands != "bf16":
             raise L.FeddatHipError("fp8=True (configs[4]) pairs the e4m3 products with bf16 operands")
-        self._init_loss_scale(operands, loss_scale, dynamic_loss_scale, scale_growth_interval)
         # fp8 (round 5): the attention backward writes dq | dk | dv as MX-scaled e4m3 (one E8M0 scale per (row, 32 columns):
         # feddat_attn_bwd_fp8mx) and QKV^T runs on the block-scaled fp8 MFMA with those scales (feddat_gemm_fp8mx_nt): the seventh
         # of the eight frozen products per layer, and half the bytes of the backward's largest write
         self.fp8_mx_dqkv = bool(fp8) and bool(fp8_mx_dqkv)
-        self._init(params, tasks, device, batch, res, text_len, layers, num_labels, lr, weight_decay, adam_eps, wgrad_splits,
-                   fp8, fp8_ffn_chain, gelu_codes)
+        super().__init__(params, tasks, device, batch, res, text_len, layers, num_labels, lr, weight_decay, adam_eps, gelu_codes,
+                         operands, loss_scale, dynamic_loss_scale, scale_growth_interval)
+        self._init_dat(params, wgrad_splits, fp8, fp8_ffn_chain, gelu_codes)
 
     @_bound
-    def _init(self, params, tasks, device, batch, res, text_len, layers, num_labels, lr, weight_decay, adam_eps, wgrad_splits,
-              fp8, fp8_ffn_chain, gelu_codes):
-        L.load()
-        self.dev = torch.device(device)
-        self.tasks = list(tasks)
-        self.B, self.Lt, self.nl = batch, text_len, layers
-        self.res = (res, res) if isinstance(res, int) else tuple(res)      # (height, width), multiples of 32
-        self.H, self.I, self.heads, self.r, self.C = 768, 3072, 12, 48, num_labels
-        self.P = 32
-        self.gh, self.gw = self.res[0] // self.P, self.res[1] // self.P
-        self.np = self.gh * self.gw
-        self.S = text_len + 1 + self.np
-        self.R = batch * self.S
-        self.lr, self.wd, self.eps = lr, weight_decay, adam_eps
+    def _init_dat(self, params, wgrad_splits, fp8, fp8_ffn_chain, gelu_codes):
+        """What the dual-adapter step owns on top of the backbone: the adapters, their workspace, the fp8 copies."""
+        dev, H, I, layers = self.dev, self.H, self.I, self.nl
+        self.r = 48
         self.fp8 = bool(fp8)
         self.fp8_ffn_chain = bool(fp8_ffn_chain)      # fp8: also FFN2 forward and FFN1^T (their A operands leave as e4m3)
         # fp8 attribution switches (tools/fp8_noise_attribution.py; production = both True): the backward's dX products on e4m3
@@ -106,90 +92,17 @@ class ViltDatEngine(LocalUpdateEngine):
         self.fp8_backward = True
         self.fp8_forward = True
         self.ksplit = wgrad_splits
-        self.ln_eps = 1e-12
-        dev = self.dev
-        H, I = self.H, self.I
+        if self.fp8:
+            self._init_fp8_weights(params)
 
-        def P(name):
-            return params[name].to(dev, torch.float32).contiguous()
-
-        def bf16_of(w):
-            out = torch.empty(w.shape, dtype=self.op_dtype, device=dev)
-            L.cvt_f32_bf16(w, out)
-            return out
-
-        def bf16_T(w):  # [R,C] fp32 -> [C,R] bf16
-            out = torch.empty(w.shape[1], w.shape[0], dtype=self.op_dtype, device=dev)
-            L.transpose_f32_bf16(w, out, w.shape[0], w.shape[1])
-            return out
-
-        def fp8_of(w):  # [N,K] fp32 -> e4m3 [N,K] + per-output-channel scale [N]
-            w8 = torch.empty(w.shape, dtype=torch.uint8, device=dev)
-            sc = torch.empty(w.shape[0], device=dev)
-            L.quant_rows_fp8(w.contiguous(), w8, sc)
-            return w8, sc
-
-        # ---------------- frozen backbone (bf16 weights + their transposes for the dX products) --------------
-        e = ENC + "embeddings."
-        self.emb = {k: P(e + k) for k in (
-            "text_embeddings.word_embeddings.weight", "text_embeddings.position_embeddings.weight",
-            "text_embeddings.token_type_embeddings.weight", "text_embeddings.LayerNorm.weight",
-            "text_embeddings.LayerNorm.bias", "patch_embeddings.projection.bias")}
-        tok = P(e + "token_type_embeddings.weight")
-        self.mod0, self.mod1 = tok[0].contiguous(), tok[1].contiguous()
-        self.cls = P(e + "cls_token").reshape(H).contiguous()
-        pos = P(e + "position_embeddings")[0]
-        self.pos0 = pos[0].contiguous()
-        # per-sample position grids: the 12 x 12 table resized to each sample's valid patch rectangle (pixel_mask)
-        self.pos_grid = pos[1:].contiguous()
-        self.g0 = int(round(math.sqrt(pos.shape[0] - 1)))
-        self.pos_img = torch.empty(batch, self.np, H, device=dev)
-        self.w_patch = bf16_of(P(e + "patch_embeddings.projection.weight").reshape(H, 3 * self.P * self.P))
-        self.layers: List[dict] = []
-        for i in range(layers):
-            Lp = ENC + f"encoder.layer.{i}."
-            wq, wk, wv = (P(Lp + f"attention.attention.{n}.weight") for n in ("query", "key", "value"))
-            wqkv = torch.cat([wq, wk, wv], 0).contiguous()
-            bqkv = torch.cat([P(Lp + f"attention.attention.{n}.bias") for n in ("query", "key", "value")]).contiguous()
-            wo, w1, w2 = P(Lp + "attention.output.dense.weight"), P(Lp + "intermediate.dense.weight"), \
-                P(Lp + self.FFN2_STEM + "weight")
-            extra = {}
-            if self.fp8:
-                extra["wqkv8"], extra["sqkv"] = fp8_of(wqkv)
-                extra["w18"], extra["s1"] = fp8_of(w1)
-                # dX products whose A operand (a gradient) is produced by a row kernel: FFN2^T and attention-output^T
-                extra["w2T8"], extra["s2T"] = fp8_of(w2.t().contiguous())
-                extra["woT8"], extra["soT"] = fp8_of(wo.t().contiguous())
-                # the FFN chain: FFN1's epilogue leaves gelu(u) as e4m3 (fixed scale) for an fp8 FFN2; FFN2^T's leaves dU as
-                # e4m3 rows that keep the incoming gradient's row scale x FEDDAT_F8_GRAD_HEADROOM (folded into W1^T's
-                # channel scales here) for an fp8 FFN1^T
-                extra["w28"], extra["s2"] = fp8_of(w2)
-                extra["w1T8"], s1T = fp8_of(w1.t().contiguous())
-                extra["s1T4"] = s1T * L.F8_GRAD_HEADROOM
-                if self.fp8_mx_dqkv:      # QKV^T: [768, 2304], per output channel
-                    extra["wqkvT8"], extra["sqkvT"] = fp8_of(wqkv.t().contiguous())
-            self.layers.append(dict(
-                extra, wqkv=bf16_of(wqkv), wqkvT=bf16_T(wqkv), bqkv=bqkv,
-                wo=bf16_of(wo), woT=bf16_T(wo), bo=P(Lp + "attention.output.dense.bias"),
-                w1=bf16_of(w1), w1T=bf16_T(w1), b1=P(Lp + "intermediate.dense.bias"),
-                w2=bf16_of(w2), w2T=bf16_T(w2), b2=P(Lp + self.FFN2_STEM + "bias"),
-                ln1g=P(Lp + "layernorm_before.weight"), ln1b=P(Lp + "layernorm_before.bias"),
-                ln2g=P(Lp + "layernorm_after.weight"), ln2b=P(Lp + "layernorm_after.bias")))
-        self.lnf_g, self.lnf_b = P(ENC + "layernorm.weight"), P(ENC + "layernorm.bias")
-        self.pool_w, self.pool_b = P(ENC + "pooler.dense.weight"), P(ENC + "pooler.dense.bias")
-
-        # ---------------- trainable state: three adapters (flat per adapter) and one head per task ----------
+        # ---------------- trainable state: three adapters (flat per adapter); the heads are the backbone's ----------
         def adapter_names(a):
             return [(ENC + f"encoder.layer.{i}.output.adapter.{self.ADAPTER_STEMS[a]}{t}",
                      {"down.weight": (self.r, H), "down.bias": (self.r,), "up.weight": (H, self.r),
                       "up.bias": (H,)}[t]) for i in range(layers) for t in ADAPTER_TENSORS]
         self.ad = [FlatGroup(adapter_names(a), dev, with_opt=(a != 2)) for a in range(len(self.ADAPTER_STEMS))]
         self.ad_layer_numel = self.r * H + self.r + H * self.r + H
-        head_shapes = {"clf_fc0.weight": (2 * H, H), "clf_fc0.bias": (2 * H,), "clf_norm0.weight": (2 * H,),
-                       "clf_norm0.bias": (2 * H,), "clf_fc1.weight": (num_labels, 2 * H), "clf_fc1.bias": (num_labels,)}
-        self.head = {t: FlatGroup([(f"task_layer.{t}.{n}", head_shapes[n]) for n in HEAD_TENSORS], dev, True)
-                     for t in self.tasks}
-        for grp in self.ad + list(self.head.values()):
+        for grp in self.ad:
             for n in grp.names:
                 grp.view(n).copy_(params[n].to(dev, torch.float32))
         # bf16 operand copies of the adapters: [a][layer] -> dict(wd, wdT, wu, wuT, bd, bu)
@@ -199,27 +112,8 @@ class ViltDatEngine(LocalUpdateEngine):
             self.repack_adapter(a)
 
         # ---------------- workspace (static: a whole step is graph-capturable) ----------------
-        R, R2, B = self.R, self.NPASS * self.R, batch
-
-        def f32(*s):
-            return torch.empty(*s, device=dev)
-
-        def b16(*s):
-            return torch.empty(*s, dtype=self.op_dtype, device=dev)
-        self._px_shape = (B, 3, self.res[0], self.res[1])
-        self.inp = dict(input_ids=torch.zeros(B, text_len, dtype=torch.int64, device=dev),
-                        token_type_ids=torch.zeros(B, text_len, dtype=torch.int64, device=dev),
-                        target=f32(B, num_labels),
-                        attention_mask=torch.ones(B, text_len, dtype=torch.int64, device=dev),
-                        # pixel_mask sampled at the patch origins (all that HF's visual_embed looks at): [B, gh, gw]
-                        patch_mask=torch.ones(B, self.gh, self.gw, dtype=torch.int64, device=dev))
-        # attention key masks of the [text | CLS | patches] sequence, derived on the device from the two HF masks
-        # inside the step (no host sync, valid for every batch under one captured graph); rows [B, 2B) repeat [0, B)
-        self.key_mask2 = torch.ones(self.NPASS * B, self.S, dtype=torch.uint8, device=dev)
-        self.patches = b16(B * self.np, 3 * self.P * self.P)
-        self.proj = f32(B * self.np, H)
-        self.h0 = f32(R, H)
-        self.x16 = b16(R2, H)          # LN output (GEMM operand), transient
+        R, R2, B = self.R, self.NPASS * self.R, self.B
+        f32, b16 = self._f32, self._b16
         if self.fp8:                   # LN output as e4m3 + per-row scale (operand of the fp8 products)
             self.x8 = torch.empty(R2, H, dtype=torch.uint8, device=dev)
             self.xs = f32(R2)
@@ -233,50 +127,18 @@ class ViltDatEngine(LocalUpdateEngine):
                     raise L.FeddatHipError("fp8_mx_dqkv needs sequences of at most 192 tokens (feddat_attn_bwd_fp8mx)")
                 self.dqkv8 = torch.empty(R2, 3 * H, dtype=torch.uint8, device=dev)        # dq | dk | dv as e4m3 ...
                 self.dqkv_sc = torch.empty(R2, 3 * H // 32, dtype=torch.uint8, device=dev)   # ... + E8M0 per (row, 32 columns)
-        self.f16 = b16(R2, I)          # gelu(u), transient
         # layer 0 (shared body, R rows): only h3 is kept
         self.l0 = dict(qkv=b16(R, 3 * H), ctx=b16(R, H), lse=f32(B, self.heads, self.S), h2=f32(R, H), h3=f32(R, H))
-        # what FFN2^T needs of the pre-GELU u: 8-bit gelu'(u) codes where the persistent GEMM applies (FEDDAT_EPI_GELU_G8 /
-        # _MUL_G8, M >= 1024: 25 % fewer bytes through the two HBM-bound epilogues), else u itself in bf16
-        self.g8u = R2 >= 1024 and bool(gelu_codes)
-
-        def u_buf():
-            return torch.empty(R2, I, dtype=torch.uint8, device=dev) if self.g8u else b16(R2, I)
-        self.act = [None] + [dict(h_in=f32(R2, H), st1=f32(R2, 2), qkv=b16(R2, 3 * H), ctx=b16(R2, H),
-                                  lse=f32(self.NPASS * B, self.heads, self.S), h2=f32(R2, H), st2=f32(R2, 2),
-                                  u=u_buf(), h3=f32(R2, H)) for _ in range(1, layers)]
+        # layers 1 .. L-1 (both passes, R2 rows): kept for the backward, each with its own input buffer (the adapter's output)
+        self.act = [None] + [self._kept_layer() for _ in range(1, layers)]
         self.h_out = f32(R2, H)        # output of the last adapter (dense path: single-layer models only)
-        # top layer: only token 0 of each sample feeds the pooler, so everything after its attention runs on 2B rows
         nb2 = self.NPASS * B
-        self.top = dict(h2=f32(nb2, H), st2=f32(nb2, 2), u=b16(nb2, I), h3=f32(nb2, H), x16=b16(nb2, H),
-                        f16=b16(nb2, I), h_out=f32(nb2, H), dh3=f32(nb2, H), dh316=b16(nb2, H), dU=b16(nb2, I),
-                        dx2=b16(nb2, H), dh2=f32(nb2, H), dh216=b16(nb2, H), dctx=f32(nb2, H))
+        self.top.update(h_out=f32(nb2, H), dh3=f32(nb2, H))
         self.st0 = f32(R, 2)
-        # head / pooler
-        self.cls_ln = f32(2 * B, H)
-        self.cls_st = f32(2 * B, 2)
-        self.pooled = f32(2 * B, H)
         # task-head activations.  P0 (gated rows, old head) and P1 (adapter_1 rows, same old head) run as ONE 2B-row
         # pass ("all" = rows [0,B), "p1" = rows [B,2B) of the "both" buffers); P2 uses the updated head.
-        both = dict(a0=f32(2 * B, 2 * H), n0=f32(2 * B, 2 * H), st=f32(2 * B, 2), g0=f32(2 * B, 2 * H),
-                    logits=f32(2 * B, num_labels))
-        self.hd = {"both": both, "all": {k: v[:B] for k, v in both.items()}, "p1": {k: v[B:] for k, v in both.items()},
-                   "p2": dict(a0=f32(B, 2 * H), n0=f32(B, 2 * H), st=f32(B, 2), g0=f32(B, 2 * H),
-                              logits=f32(B, num_labels))}
-        self.dlogits = f32(B, num_labels)
+        self.hd["p2"] = dict(a0=f32(B, 2 * H), n0=f32(B, 2 * H), st=f32(B, 2), g0=f32(B, 2 * H), logits=f32(B, self.C))
         self.loss_buf = {k: f32(4 + 2 * B) for k in ("p1", "p2")}
-        self.dg0, self.dn0, self.da0 = f32(B, 2 * H), f32(B, 2 * H), f32(B, 2 * H)
-        self.dpooled = f32(2 * B, H)
-        self.dpre = f32(2 * B, H)
-        self.dcls_ln = f32(2 * B, H)
-        self.dcls = f32(2 * B, H)
-        # backward streams
-        self.dh = [f32(R2, H), f32(R2, H)]       # ping-pong residual-gradient stream
-        self.dh16 = b16(R2, H)
-        self.dU = b16(R2, I)
-        self.dx16 = b16(R2, H)
-        self.dctx = b16(R2, H)
-        self.dqkv = b16(R2, 3 * H)
         self.z = f32(R2, self.r)
         self.dz = f32(R2, self.r)
         # relu(W_down h3 + b_down) of every adapter slot, saved by the adapter forward of each layer for its backward
@@ -288,32 +150,50 @@ class ViltDatEngine(LocalUpdateEngine):
         self.wpart_all = f32(layers * self.wpart_stride)
         self.wpart = self.wpart_all[:self.wpart_stride]
         self._segs_cache: Dict = {}
-        self.graph = None
-        self.ctx = L.Context(self.dev.index if self.dev.index is not None else torch.cuda.current_device())
         self._layer_structs: Dict = {}
         # True: one composite C-ABI call per middle layer (feddat_vilt_layer_fwd / _bwd); False: the same kernel sequence
         # issued op by op from here (what tools/step_breakdown.py brackets with events)
         self.use_layer_calls = bool(gelu_codes) or R2 < 1024      # (the composite layer calls take the code epilogues at M >= 1024)
-        # True: the serial tail (token-0 LayerNorm + pooler, task head forward / backward, loss, optimizer bookkeeping) on the
-        # fused kernels of csrc/head_tail.hip (20 launches); False: the round-3 sequence of 46 single-purpose launches (same
-        # arithmetic up to fp32 summation order; tools/step_breakdown.py --unfused-tail, and the tests compare the two)
-        self.fused_tail = True
-        # True: the last layer's attention computes the ONE query per (sample, head) the pooler consumes (token 0) and its
-        # rank-1 backward (feddat_attn_cls_fwd / _bwd); False: the dense kernels on all S queries (184 of 185 never read)
-        self.cls_attention = True
         # True: with the token-0-only attention the last layer's QKV product computes K | V for every row and Q for the 2B token-0
         # rows only, and QKV^T contracts dK | dV densely + the token-0 rows' dQ as a skinny product (a third of both products:
         # -0.03 ms/step, ratio 0.996).  OFF by default: equally accurate, but not bit-identical on the 2B token-0 rows, and at 80
         # steps the AdamW trajectory is chaotic enough that this moves the draw of the round-length parity tests (DESIGN.md
         # section 5, "draws"): the default keeps round 5's arithmetic, whose draws on both reference rounds are pinned.
         self.top_q_cls = False
-        self.sched = dict(warmup=1, total=2)
         self.opt_adapters = (0, 1)
-        self.task = self.tasks[0]
-        # dynamic loss scale (GradScaler on the device); the head's p | m | v before its sub-step-A update (restored when A
-        # turns out to have overflowed in the backbone's backward)
-        self._alloc_scaler()
+        # the head's p | m | v before its sub-step-A update (restored when A turns out to have overflowed in the backbone's
+        # backward under the dynamic loss scale)
         self.head_bak = {t: torch.empty(3 * self.head[t].p.numel(), device=dev) for t in self.tasks} if self.dynamic_scale else {}
+
+    def _init_fp8_weights(self, params):
+        """e4m3 copies of the frozen weights of the fp8 products, quantised once per output channel of each product."""
+        dev = self.dev
+
+        def fp8_of(w):  # [N,K] fp32 -> e4m3 [N,K] + per-output-channel scale [N]
+            w8 = torch.empty(w.shape, dtype=torch.uint8, device=dev)
+            sc = torch.empty(w.shape[0], device=dev)
+            L.quant_rows_fp8(w.contiguous(), w8, sc)
+            return w8, sc
+
+        for i, W in enumerate(self.layers):
+            Lp = ENC + f"encoder.layer.{i}."
+            wqkv = torch.cat([self._param(params, Lp + f"attention.attention.{n}.weight") for n in ("query", "key", "value")],
+                             0).contiguous()
+            wo, w1, w2 = (self._param(params, Lp + n + "weight") for n in ("attention.output.dense.", "intermediate.dense.",
+                                                                            self.FFN2_STEM))
+            W["wqkv8"], W["sqkv"] = fp8_of(wqkv)
+            W["w18"], W["s1"] = fp8_of(w1)
+            # dX products whose A operand (a gradient) is produced by a row kernel: FFN2^T and attention-output^T
+            W["w2T8"], W["s2T"] = fp8_of(w2.t().contiguous())
+            W["woT8"], W["soT"] = fp8_of(wo.t().contiguous())
+            # the FFN chain: FFN1's epilogue leaves gelu(u) as e4m3 (fixed scale) for an fp8 FFN2; FFN2^T's leaves dU as
+            # e4m3 rows that keep the incoming gradient's row scale x FEDDAT_F8_GRAD_HEADROOM (folded into W1^T's
+            # channel scales here) for an fp8 FFN1^T
+            W["w28"], W["s2"] = fp8_of(w2)
+            W["w1T8"], s1T = fp8_of(w1.t().contiguous())
+            W["s1T4"] = s1T * L.F8_GRAD_HEADROOM
+            if self.fp8_mx_dqkv:      # QKV^T: [768, 2304], per output channel
+                W["wqkvT8"], W["sqkvT"] = fp8_of(wqkv.t().contiguous())
 
     # ------------------------------------------------------------------------------------------ adapters
     def _alloc_pack(self, a, i):
@@ -365,97 +245,30 @@ class ViltDatEngine(LocalUpdateEngine):
             ads = [dict(self.ad16[int(mode.split("_")[1])][layer], scale=1.0)]
         return L.make_segs([dict(row_begin=0, row_end=rows, adapters=ads)])
 
-    # ------------------------------------------------------------------------------------------ inputs
-    @_bound
-    def set_batch(self, batch: Dict[str, torch.Tensor]):
-        """Copy one batch (reference schema: HF ViLT encodings + target_scores) into the static input buffers."""
-        px = batch["pixel_values"]
-        if tuple(px.shape) != self._px_shape:
-            raise L.FeddatHipError(f"engine built for pixel_values {self._px_shape}, got {tuple(px.shape)}")
-        # the pixels are consumed right here, from the caller's tensor: patch extraction (im2col + bf16) is the only reader of
-        # pixel_values, so it runs ahead of the captured step instead of a 57 MB device-to-device copy into a static buffer
-        # followed by the same read inside the graph (stream-ordered with the replay that follows)
-        if not px.is_cuda:
-            px = px.to(self.dev, non_blocking=True)
-        L.im2col_patches(px.to(torch.float32).contiguous(), self.patches, self.B, 3, self.res[0], self.res[1], self.P)
-        ids, tts, am, tg, pm = (batch.get(k) for k in ("input_ids", "token_type_ids", "attention_mask", "target_scores",
-                                                        "pixel_mask"))
-
-        def dev_ok(t, dt, shape):
-            return t is None or (t.is_cuda and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == shape)
-        B, Lt = self.B, self.Lt
-        if (ids is not None and tts is not None and dev_ok(ids, torch.int64, (B, Lt)) and dev_ok(tts, torch.int64, (B, Lt))
-                and dev_ok(am, torch.int64, (B, Lt)) and dev_ok(tg, torch.float32, (B, self.C))
-                and dev_ok(pm, torch.int64, (B, self.res[0], self.res[1]))):
-            # the usual case (device-resident batch in the reference's dtypes): one launch for all five
-            L.vilt_stage_inputs(ids, tts, am, tg, pm, self.inp, B, Lt, self.C, self.res[0], self.res[1], self.P)
-            return
-        self.inp["input_ids"].copy_(batch["input_ids"], non_blocking=True)
-        self.inp["token_type_ids"].copy_(batch["token_type_ids"], non_blocking=True)
-        if "target_scores" in batch:
-            self.inp["target"].copy_(batch["target_scores"], non_blocking=True)
-        if batch.get("attention_mask") is not None:     # absent = all valid
-            self.inp["attention_mask"].copy_(batch["attention_mask"], non_blocking=True)
-        else:
-            self.inp["attention_mask"].fill_(1)
-        if batch.get("pixel_mask") is not None:
-            self.inp["patch_mask"].copy_(batch["pixel_mask"][:, ::self.P, ::self.P], non_blocking=True)
-        else:
-            self.inp["patch_mask"].fill_(1)
-
     # ------------------------------------------------------------------------------------------ forward
-    def _embed(self):
-        B, H, S, Lt = self.B, self.H, self.S, self.Lt
-        e = self.emb
-        L.text_embed(self.inp["input_ids"], self.inp["token_type_ids"], e["text_embeddings.word_embeddings.weight"],
-                     e["text_embeddings.position_embeddings.weight"], e["text_embeddings.token_type_embeddings.weight"],
-                     e["text_embeddings.LayerNorm.weight"], e["text_embeddings.LayerNorm.bias"], self.ln_eps,
-                     self.mod0, self.h0, B, Lt, S, H)
-        # (self.patches was filled by set_batch: im2col of the caller's pixel_values)
-        L.gemm_bf16_nt(self.patches, self.w_patch, L.EPI_F32, bias=e["patch_embeddings.projection.bias"],
-                       out_f32=self.proj)
-        if self.fused_tail:      # key mask + per-sample position grid + assembly in one launch (bit-identical)
-            L.image_embed_assemble_masked(self.proj, self.cls, self.pos0, self.pos_grid, self.inp["patch_mask"],
-                                          self.inp["attention_mask"], self.mod1, self.h0, self.key_mask2, B, Lt, self.gh,
-                                          self.gw, self.g0, H, nrep=self.NPASS)
-            return
-        L.vilt_key_mask(self.inp["attention_mask"], self.inp["patch_mask"], self.key_mask2, B, Lt, self.gh, self.gw, 1,
-                        nrep=self.NPASS)
-        L.pos_embed_resize_masked(self.pos_grid, self.inp["patch_mask"], self.pos_img, self.g0, B, self.gh, self.gw, 1,
-                                  H)
-        L.image_embed_assemble(self.proj, self.cls, self.pos0, self.pos_img, self.mod1, self.h0, B, Lt, self.np, S, H,
-                               pos_batch_stride=self.np * H)
-
     def _layer_body(self, i: int, h_in, rows: int, nb: int, qkv, ctx, lse, h2, h3, st1=None, st2=None, u=None,
                     mask=None, ln1_done=False):
-        """LN -> QKV -> attention -> out-proj(+res) -> LN -> FFN1(gelu) -> FFN2(+res): HF ViltLayer with the
-        Adaptered_ViltOutput dense+residual (adaptered_output.py:74-76); returns the adapter input in h3."""
+        """The backbone's layer body; where the fp8 products apply (_fp8_rows), the two products fed by a LayerNorm -- and with
+        fp8_ffn_chain FFN2 -- run on the fp8 MFMA."""
+        if not self._fp8_rows(rows):
+            return super()._layer_body(i, h_in, rows, nb, qkv, ctx, lse, h2, h3, st1=st1, st2=st2, u=u, mask=mask,
+                                       ln1_done=ln1_done)
         W, H = self.layers[i], self.H
-        x16, f16 = self.x16[:rows], self.f16[:rows]
+        f16 = self.f16[:rows]
         g8 = u is not None and u.dtype == torch.uint8
-        if self._fp8_rows(rows):           # fp8 MFMA for the two products fed by a LayerNorm
-            x8, xs = self.x8[:rows], self.xs[:rows]
-            L.layernorm_fwd_fp8(h_in, W["ln1g"], W["ln1b"], self.ln_eps, rows, H, x8, xs, stats=st1)
-            L.gemm_fp8_nt(x8, xs, W["wqkv8"], W["sqkv"], L.EPI_BF16, bias=W["bqkv"], out_bf16=qkv)
-            L.attn_fwd(qkv, ctx, lse, nb, self.S, self.heads, key_mask=mask)
-            L.gemm_bf16_nt(ctx, W["wo"], L.EPI_RESID_F32, bias=W["bo"], resid=h_in, out_f32=h2)
-            L.layernorm_fwd_fp8(h2, W["ln2g"], W["ln2b"], self.ln_eps, rows, H, x8, xs, stats=st2)
-            if self.fp8_ffn_chain:      # FFN1 -> e4m3 gelu(u) (+ gelu' codes) -> fp8 FFN2
-                codes = u if g8 else self.dU.view(torch.uint8)[:rows, :self.I]       # (no backward through this call: scratch)
-                L.gemm_fp8_nt(x8, xs, W["w18"], W["s1"], L.EPI_GELU_G8_F8, bias=W["b1"], out_bf16=self.f8[:rows], out2_bf16=codes)
-                L.gemm_fp8_nt_f32(self.f8[:rows], self.f8s[:rows], W["w28"], W["s2"], bias=W["b2"], resid=h2, out_f32=h3)
-                return
-            L.gemm_fp8_nt(x8, xs, W["w18"], W["s1"], L.EPI_GELU_G8 if g8 else L.EPI_GELU, bias=W["b1"], out_bf16=f16,
-                          out2_bf16=u if u is not None else self.dU[:rows])
-            L.gemm_bf16_nt(f16, W["w2"], L.EPI_RESID_F32, bias=W["b2"], resid=h2, out_f32=h3)
-            return
-        if not ln1_done:     # otherwise x16 / st1 were written by the previous layer's fused adapter + LN kernel
-            L.layernorm_fwd(h_in, W["ln1g"], W["ln1b"], self.ln_eps, rows, H, y_bf16=x16, stats=st1)
-        L.gemm_bf16_nt(x16, W["wqkv"], L.EPI_BF16, bias=W["bqkv"], out_bf16=qkv)
+        x8, xs = self.x8[:rows], self.xs[:rows]
+        L.layernorm_fwd_fp8(h_in, W["ln1g"], W["ln1b"], self.ln_eps, rows, H, x8, xs, stats=st1)
+        L.gemm_fp8_nt(x8, xs, W["wqkv8"], W["sqkv"], L.EPI_BF16, bias=W["bqkv"], out_bf16=qkv)
         L.attn_fwd(qkv, ctx, lse, nb, self.S, self.heads, key_mask=mask)
         L.gemm_bf16_nt(ctx, W["wo"], L.EPI_RESID_F32, bias=W["bo"], resid=h_in, out_f32=h2)
-        L.layernorm_fwd(h2, W["ln2g"], W["ln2b"], self.ln_eps, rows, H, y_bf16=x16, stats=st2)
-        L.gemm_bf16_nt(x16, W["w1"], L.EPI_GELU_G8 if g8 else L.EPI_GELU, bias=W["b1"], out_bf16=f16, out2_bf16=u)
+        L.layernorm_fwd_fp8(h2, W["ln2g"], W["ln2b"], self.ln_eps, rows, H, x8, xs, stats=st2)
+        if self.fp8_ffn_chain:      # FFN1 -> e4m3 gelu(u) (+ gelu' codes) -> fp8 FFN2
+            codes = u if g8 else self.dU.view(torch.uint8)[:rows, :self.I]       # (no backward through this call: scratch)
+            L.gemm_fp8_nt(x8, xs, W["w18"], W["s1"], L.EPI_GELU_G8_F8, bias=W["b1"], out_bf16=self.f8[:rows], out2_bf16=codes)
+            L.gemm_fp8_nt_f32(self.f8[:rows], self.f8s[:rows], W["w28"], W["s2"], bias=W["b2"], resid=h2, out_f32=h3)
+            return
+        L.gemm_fp8_nt(x8, xs, W["w18"], W["s1"], L.EPI_GELU_G8 if g8 else L.EPI_GELU, bias=W["b1"], out_bf16=f16,
+                      out2_bf16=u if u is not None else self.dU[:rows])
         L.gemm_bf16_nt(f16, W["w2"], L.EPI_RESID_F32, bias=W["b2"], resid=h2, out_f32=h3)
 
     def _fp8_rows(self, rows: int, bwd: bool = False) -> bool:
@@ -504,26 +317,6 @@ class ViltDatEngine(LocalUpdateEngine):
         else:
             self._pool(self.h_out, nb)
 
-    def _sg(self, A, sa_i, sa_k, Bm, sb_k, sb_j, I, J, K, out, ksplit=1, bias_j=None, alpha=1.0):
-        """Skinny exact-fp32 product; long contractions are split over the grid and reduced deterministically."""
-        if ksplit <= 1:
-            L.sgemm_f32(A, sa_i, sa_k, Bm, sb_k, sb_j, I, J, K, out, bias_j=bias_j, alpha=alpha)
-            return
-        part = self._scratch1(ksplit * I * J)
-        L.sgemm_f32(A, sa_i, sa_k, Bm, sb_k, sb_j, I, J, K, part, ksplit=ksplit, bias_j=bias_j,
-                    out_split_stride=I * J, alpha=alpha)
-        L.reduce_partials(part, I * J, ksplit, I * J, out)
-
-    def _scratch1(self, n):
-        if not hasattr(self, "_scr") or self._scr.numel() < n:
-            self._scr = torch.empty(n, device=self.dev)
-        return self._scr
-
-    def _cls_rows(self, t, nb: int):
-        """Strided view of token 0 of every sample: [nb, width] with row stride S * width (no copy)."""
-        w = t.shape[1]
-        return t.view(nb, self.S * w)[:, :w]
-
     def _top_layer_fwd(self, mask):
         """Last layer.  LN1 / QKV / attention see every token (keys and values of all tokens feed token 0), but only
         token 0 of each sample reaches the pooler (HF ViltPooler takes hidden_states[:, 0]; vilt.py:127), so the
@@ -547,23 +340,8 @@ class ViltDatEngine(LocalUpdateEngine):
             L.gemm_bf16_nt(x16, W["wqkv"], L.EPI_BF16, bias=W["bqkv"], out_bf16=a["qkv"])
         (L.attn_cls_fwd if self.cls_attention else L.attn_fwd)(a["qkv"], a["ctx"], a["lse"], nb, self.S, self.heads,
                                                                 key_mask=mask)
-        L.gemm_bf16_nt(self._cls_rows(a["ctx"], nb), W["wo"], L.EPI_RESID_F32, bias=W["bo"],
-                       resid=self._cls_rows(a["h_in"], nb), out_f32=t["h2"], skinny_workspace=self._skinny_ws())
-        L.layernorm_fwd(t["h2"], W["ln2g"], W["ln2b"], self.ln_eps, nb, H, y_bf16=t["x16"], stats=t["st2"])
-        L.gemm_bf16_nt(t["x16"], W["w1"], L.EPI_GELU, bias=W["b1"], out_bf16=t["f16"], out2_bf16=t["u"],
-                       skinny_workspace=self._skinny_ws())
-        L.gemm_bf16_nt(t["f16"], W["w2"], L.EPI_RESID_F32, bias=W["b2"], resid=t["h2"], out_f32=t["h3"],
-                       skinny_workspace=self._skinny_ws())
+        self._top_token0_fwd(a, W, nb)
         L.adapter_fwd(t["h3"], t["h_out"], self._top_segs(False), nb, z_save=self.zsave[i])
-
-    def _skinny_ws(self):
-        """fp32 split-K partials of the top layer's 2B-row GEMMs (largest: 2B x 3072 x 768)."""
-        if getattr(self, "_skws", None) is None:
-            nb, H, I = self.NPASS * self.B, self.H, self.I
-            n = max(L.gemm_skinny_workspace_elems(nb, I, H), L.gemm_skinny_workspace_elems(nb, H, I),
-                    L.gemm_skinny_workspace_elems(nb, H, H), L.gemm_skinny_workspace_elems(nb, H, 3 * H)) if nb <= 64 else 0
-            self._skws = torch.empty(max(n, 1), device=self.dev) if n else False
-        return self._skws if self._skws is not False else None
 
     def _top_segs(self, bwd: bool):
         key = ("top", bwd)
@@ -576,77 +354,6 @@ class ViltDatEngine(LocalUpdateEngine):
                 dict(row_begin=B, row_end=2 * B, train_slot=0 if bwd else -1, adapters=[dict(a1, scale=1.0)]),
             ])
         return self._segs_cache[key]
-
-    def _pool(self, h_last, nb: int, x_stride: int = None):
-        """ViltModel.layernorm on token 0 + ViltPooler (dense + tanh) -> self.pooled[:nb]."""
-        H = self.H
-        self._pool_src, self._pool_stride = h_last, (self.S * H if x_stride is None else x_stride)
-        if self.fused_tail:      # LayerNorm (statistics in the block) -> dense -> tanh in one launch
-            L.head_gemm(L.ht_job(h_last, self._pool_stride, 1, self.pool_w, 1, H, nb, H, H, self.pooled, bias_j=self.pool_b,
-                                 pro=L.HT_PRO_LN, pro_a=self.lnf_g, pro_b=self.lnf_b, pro_eps=self.ln_eps,
-                                 stats_out=self.cls_st, epi=L.HT_EPI_TANH))
-            return
-        L.layernorm_fwd(h_last, self.lnf_g, self.lnf_b, self.ln_eps, nb, H, x_stride=self._pool_stride,
-                        y_f32=self.cls_ln, stats=self.cls_st)
-        self._sg(self.cls_ln, H, 1, self.pool_w, 1, H, nb, H, H, self.pooled, ksplit=4, bias_j=self.pool_b)
-        L.tanh_fwd(self.pooled[:nb])
-
-    def _head_fwd(self, pooled, slot: str, task: str):
-        """vilt.py:202-209: fc0 -> LayerNorm(1536, eps 1e-5) -> GELU -> fc1 on the rows of `pooled` (B, or 2B for the
-        joint P0 + P1 pass)."""
-        B, H, C = pooled.shape[0], self.H, self.C
-        hp, s = self.head[task], self.hd[slot]
-        pre = f"task_layer.{task}."
-        if self.fused_tail:
-            L.head_gemm(L.ht_job(pooled, H, 1, hp.view(pre + "clf_fc0.weight"), 1, H, B, 2 * H, H, s["a0"],
-                                 bias_j=hp.view(pre + "clf_fc0.bias")))
-            L.head_ln_gelu(s["a0"], hp.view(pre + "clf_norm0.weight"), hp.view(pre + "clf_norm0.bias"), 1e-5, s["n0"], s["st"],
-                           s["g0"])
-            L.head_gemm(L.ht_job(s["g0"], 2 * H, 1, hp.view(pre + "clf_fc1.weight"), 1, 2 * H, B, C, 2 * H, s["logits"],
-                                 bias_j=hp.view(pre + "clf_fc1.bias")))
-            return s["logits"]
-        self._sg(pooled, H, 1, hp.view(pre + "clf_fc0.weight"), 1, H, B, 2 * H, H, s["a0"], ksplit=4,
-                 bias_j=hp.view(pre + "clf_fc0.bias"))
-        L.layernorm_fwd(s["a0"], hp.view(pre + "clf_norm0.weight"), hp.view(pre + "clf_norm0.bias"), 1e-5, B, 2 * H,
-                        y_f32=s["n0"], stats=s["st"])
-        L.gelu_fwd(s["n0"], s["g0"])
-        self._sg(s["g0"], 2 * H, 1, hp.view(pre + "clf_fc1.weight"), 1, 2 * H, B, C, 2 * H, s["logits"], ksplit=16,
-                 bias_j=hp.view(pre + "clf_fc1.bias"))
-        return s["logits"]
-
-    def _head_bwd(self, pooled, slot: str, task: str, dpooled_out):
-        """Gradients of the task head (all six tensors, fp32) and d(pooled) for B rows."""
-        B, H, C = self.B, self.H, self.C
-        hp, s = self.head[task], self.hd[slot]
-        pre = f"task_layer.{task}."
-
-        def G(n):
-            return hp.view(pre + n, hp.g)
-        dl = self.dlogits
-        if self.fused_tail:
-            # {dW_fc1 = dl^T g0, db_fc1} next to {dn0 = (dl W_fc1) * gelu'(n0)}; LayerNorm backward (dx, dgamma, dbeta);
-            # {dW_fc0 = da0^T pooled, db_fc0} next to {dpooled = da0 W_fc0}: three launches
-            L.head_gemm(L.ht_job(dl, 1, C, s["g0"], 2 * H, 1, C, 2 * H, B, G("clf_fc1.weight"), mode=1, colsum=G("clf_fc1.bias")),
-                        L.ht_job(dl, C, 1, hp.view(pre + "clf_fc1.weight"), 2 * H, 1, B, 2 * H, C, self.dn0,
-                                 epi=L.HT_EPI_MUL_DGELU, aux=s["n0"], ld_aux=2 * H))
-            L.head_ln_bwd_full(self.dn0, s["a0"], s["st"], hp.view(pre + "clf_norm0.weight"), self.da0, G("clf_norm0.weight"),
-                               G("clf_norm0.bias"))
-            L.head_gemm(L.ht_job(self.da0, 1, 2 * H, pooled, H, 1, 2 * H, H, B, G("clf_fc0.weight"), mode=1,
-                                 colsum=G("clf_fc0.bias")),
-                        L.ht_job(self.da0, 2 * H, 1, hp.view(pre + "clf_fc0.weight"), H, 1, B, H, 2 * H, dpooled_out))
-            return
-        L.sgemm_f32(dl, 1, C, s["g0"], 2 * H, 1, C, 2 * H, B, G("clf_fc1.weight"), colsum=G("clf_fc1.bias"))
-        L.sgemm_f32(dl, C, 1, hp.view(pre + "clf_fc1.weight"), 2 * H, 1, B, 2 * H, C, self.dg0)
-        L.gelu_bwd(s["n0"], self.dg0, self.dn0)
-        L.layernorm_bwd_full(self.dn0, s["a0"], s["st"], hp.view(pre + "clf_norm0.weight"), B, 2 * H, self.da0,
-                             G("clf_norm0.weight"), G("clf_norm0.bias"))
-        L.sgemm_f32(self.da0, 1, 2 * H, pooled, H, 1, 2 * H, H, B, G("clf_fc0.weight"), colsum=G("clf_fc0.bias"))
-        self._sg(self.da0, 2 * H, 1, hp.view(pre + "clf_fc0.weight"), H, 1, B, H, 2 * H, dpooled_out, ksplit=8)
-
-    def _adamw(self, grp: FlatGroup):
-        """One group's AdamW as its own launch (the unfused tail)."""
-        L.adamw_flat(grp.p, grp.g, grp.m, grp.v, grp.seg_off, self._wd_vec(grp), grp.state, self.lr,
-                     self.sched["warmup"], self.sched["total"], 0.9, 0.98, self.eps)
 
     # ------------------------------------------------------------------------------------------ backward
     @_bound
@@ -815,15 +522,6 @@ class ViltDatEngine(LocalUpdateEngine):
         # flags[a] for adapter a
         self._reduce_wgrads(self._segs_cache[key], self.nl, len(ads), self.wpart_all, self.wpart_stride, self.ovf_flags[ads[0]:])
 
-    def _dyn(self) -> bool:
-        """Dynamic loss scale in effect (it rides on the fused tail's multi-group AdamW launch)."""
-        return self.dynamic_scale and self.fused_tail
-
-    def _scale_in(self):
-        """How the loss scale enters the backbone's backward (factor of the pooler-backward product); it leaves through
-        _scale_out."""
-        return dict(alpha=1.0, alpha_dev=self.scaler_f[0:1]) if self._dyn() else dict(alpha=self.loss_scale)
-
     def _adapter_wgrads(self, layer: int, x, x_delta_s: int, dy):
         """dW_up = s dy^T z, db_up = s sum_t dy, dW_down = dz^T x, db_down = sum_t dz (autograd of adapter.py:125-146)
         for adapter_0 (rows [0,R)) and adapter_1 (rows [R,2R)): exact fp32 MFMA, split over tokens, deterministic
@@ -844,14 +542,10 @@ class ViltDatEngine(LocalUpdateEngine):
         self._start_local_update(steps_per_epoch, num_epochs, warmup_ratio, {"adapter_0": (1, 0)})
 
     def _graph_switches(self) -> Tuple:
-        return (self.task, self.use_layer_calls, self.fp8, self.fp8_ffn_chain, self.fused_tail, self.cls_attention,
-                self.fp8_mx_dqkv, self.top_q_cls)
+        return super()._graph_switches() + (self.use_layer_calls, self.fp8, self.fp8_ffn_chain, self.fp8_mx_dqkv, self.top_q_cls)
 
     def _named_groups(self):
         return [("adapter_0", self.ad[0]), ("adapter_1", self.ad[1]), ("head", self.head[self.task])]
-
-    def _state_groups(self):
-        return self.ad + list(self.head.values())
 
     def _loss(self, logits, teacher, slot):
         if self._dyn():      # + non-finite loss -> the sub-step's overflow flag (p1 = sub-step A, p2 = B)

@@ -83,7 +83,7 @@ def make_rccl_comm(world: int, rank: int):
 
 
 def allreduce_average(engine, world: int, num: float = 1.0, total: float = None, comm=None):
-    """One client per GPU: adapter_1 <- sum_k adapter_1[k] * num_k / total.  With `comm` (L.RcclComm) the whole exchange is
+    """One client per GPU: comm_flat() (adapter_1 of a DAT engine) <- sum_k comm_flat()[k] * num_k / total.  With `comm` (L.RcclComm) the whole exchange is
     the C-ABI call feddat_fedavg_allreduce; otherwise torch.distributed issues the all-reduce (backend "nccl" == RCCL)."""
     flat = engine.comm_flat()
     if not hasattr(engine, "_fedavg_buf"):
@@ -93,5 +93,5 @@ def allreduce_average(engine, world: int, num: float = 1.0, total: float = None,
         comm.fedavg_allreduce(flat, engine._fedavg_buf, num, total)
     else:
         allreduce_flat(flat, engine._fedavg_buf, num, total)
-    engine.repack_adapter(1)
+    engine.comm_written()
     return flat

@@ -1,10 +1,11 @@
-"""Host-side protocol that every local-update engine shares around its HIP step (ViltDatEngine, ViltAdapterEngine,
-ViltVectorEngine, AlbefDatEngine): the flat trainable groups, the device-side loss scaler (GradScaler on the device), the
-AdamW launches and the DAT optimizer tail, the start of a local update, hipGraph capture, and the trainable state.
+"""Host-side protocol that every local-update engine shares around its HIP step (the ViLT engines on vilt_backbone.ViltBackbone --
+ViltDatEngine, ViltAdapterEngine, ViltVectorEngine -- and AlbefDatEngine): the flat trainable groups, the device-side loss scaler
+(GradScaler on the device), the AdamW launches and the DAT optimizer tail, the start of a local update,
+hipGraph capture, and the trainable state.
 
-An engine derived from LocalUpdateEngine supplies its step (`_step_kernels`), its adapters (`ad`, `repack_adapter`), the
-(name, group) pairs a train_step updates (`_named_groups`), the host-side switches frozen into a captured step
-(`_graph_switches`) and the tensor train_step returns (`_loss_tensor`)."""
+An engine derived from LocalUpdateEngine supplies its step (`_step_kernels`), its adapters (`ad`, `repack_adapter`; an engine
+without adapters: `ad = []`), the (name, group) pairs a train_step updates (`_named_groups`), the host-side switches frozen into a
+captured step (`_graph_switches`) and the tensor train_step returns (`_loss_tensor`)."""
 from __future__ import annotations
 
 import functools
@@ -275,6 +276,16 @@ class LocalUpdateEngine:
     def comm_flat(self) -> torch.Tensor:
         """The FedAvg payload: every tensor of the averaged adapter back-to-back in state-dict order (main.py:154-163,499-503)."""
         return self.ad[self.COMM_ADAPTER].p
+
+    def comm_written(self):
+        """To be called after comm_flat() was overwritten (a server copy, the FedAvg write-back): rebuilds what the step derives
+        from it, the averaged adapter's 16-bit operand copies."""
+        self.repack_adapter(self.COMM_ADAPTER)
+
+    def repack(self):
+        """Rebuild the 16-bit operand copies of every adapter (after tensors were written into state_dict()'s views)."""
+        for a in range(len(self.ad)):
+            self.repack_adapter(a)
 
     def nonfinite_groups(self) -> List[str]:
         """Names of the trainable groups holding an inf / NaN (one host read-back each); [] = all finite (train.main agrees on

@@ -274,8 +274,7 @@ class ViltContinualLearner:
         self.engine.load_tensors({k: v for k, v in sd.items() if k in own})
 
     def after_load(self):
-        for a in range(len(self.engine.ad)):
-            self.engine.repack_adapter(a)
+        self.engine.repack()
 
     # ---- the reference's batch schema (vilt.py:87-100): images + questions -> HF ViLT encodings, on the device ----
     @property

@@ -435,7 +435,6 @@ def main(argv=None):
     def personal(sd):
         keep = set(mode_names(list(sd), mode)["personal"])
         return {n: v.clone() for n, v in sd.items() if n in keep}
-    comm_slot = 1 if mode == "dat" else 0       # the engine's adapter slot behind comm_flat()
     personal_params = {t: personal(model.state_dict()) for t in my_tasks}
     def make_batch(seed, ti=0):
         if albef:
@@ -481,7 +480,7 @@ def main(argv=None):
         nonfinite = []
         for k, task_key in enumerate(my_tasks):
             eng.comm_flat().copy_(server_flat)                      # main.py:472 deepcopy(server)
-            eng.repack_adapter(comm_slot)
+            eng.comm_written()
             model.load_state_dict(personal_params[task_key])        # main.py:473-478
             model.adapter_requires_grad = dict(server_flags)
             trainer = Trainer(args, task_key, data[task_key], data[task_key][:2], log)
@@ -535,7 +534,7 @@ def main(argv=None):
             # (create_optimizer filters on requires_grad, task_trainer.py:477-504) no longer holds adapter_0.
             server_flags.update({0: False, 1: True})
     eng.comm_flat().copy_(server_flat)
-    eng.repack_adapter(comm_slot)
+    eng.comm_written()
     if rccl is not None:
         torch.cuda.synchronize()
         rccl.close()

@@ -4,8 +4,9 @@ The reference's non-dat train_step (src/train/visionlanguage_tasks/task_trainer.
 anywhere -- with requires_grad on every parameter whose name contains 'bias' resp. 'norm' plus the task head (main.py:176-196,
 246-250): one forward, loss = BCEWithLogits_mean * C, one backward, one AdamW step over {vectors, head}, one scheduler tick.
 
-The frozen forward and the dX chain of the backward are the kernels of engine.ViltDatEngine at R = B * S rows; what is new is
-that the backward runs THROUGH layer 0 and that after each gradient tensor exists its per-column vector gradient is taken
+The frozen forward is vilt_backbone.ViltBackbone's at R = B * S rows and the dX chain of the backward is the dual-adapter
+engine's kernels (engine.py) without the adapter; what is new is that the backward runs THROUGH layer 0 and that after each
+gradient tensor exists its per-column vector gradient is taken
 (csrc/vector_grad.hip: feddat_colsum_partial / feddat_ln_param_grad_partial into per-vector partial buffers, then ONE
 feddat_vector_grad_reduce per step that unscales by the device-side 1 / loss-scale and feeds the overflow flag):
 
@@ -21,7 +22,7 @@ feddat_vector_grad_reduce per step that unscales by the device-side 1 / loss-sca
   rows) and patch_embeddings.projection.bias (image-patch rows; every patch row of h0 is proj + position + type, padded ones
   included, and a padded row's gradient is exactly zero because it is masked as a key and never pooled).
 
-The last layer runs ViltDatEngine's token-0 path minus its adapter (only token 0 reaches the pooler): its FFN / LN2 /
+The last layer runs the backbone's token-0 path with no adapter behind it (only token 0 reaches the pooler): its FFN / LN2 /
 attention-output gradients live on the B token-0 rows and are summed over those rows only.  'norm' mode stops after layer
 0's layernorm_before (nothing trainable below).
 
@@ -36,9 +37,9 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import torch
 
 from . import lib as L
-from .engine import ENC, ViltDatEngine
 from .local_update import FlatGroup, _bound
 from .modes import VECTOR_MODES
+from .vilt_backbone import ENC, ViltBackbone
 
 
 def vector_names(mode: str, layers: int, hidden: int = 768, inter: int = 3072) -> List[Tuple[str, Tuple[int, ...]]]:
@@ -64,28 +65,23 @@ def vector_names(mode: str, layers: int, hidden: int = 768, inter: int = 3072) -
     return out
 
 
-class ViltVectorEngine(ViltDatEngine):
-    NPASS = 1
-    ADAPTER_STEMS = ()
-    FFN2_STEM = "output.dense."
-
+class ViltVectorEngine(ViltBackbone):
     def __init__(self, params: Dict[str, torch.Tensor], tasks: Sequence[str], device, batch: int, res: int, mode: str = "bias",
                  fp8: bool = False, **kw):
-        """mode: "bias" | "norm"; other arguments as ViltDatEngine (operands "f16" -- the default, dynamic loss scale -- or
+        """mode: "bias" | "norm"; other arguments as ViltBackbone (operands "f16" -- the default, dynamic loss scale -- or
         "bf16"); fp8 is not supported."""
         if mode not in VECTOR_MODES:
             raise L.FeddatHipError(f"ViltVectorEngine runs optimizer_mode {VECTOR_MODES}, got {mode!r}")
         if fp8:
             raise L.FeddatHipError(f"optimizer_mode {mode} runs with 16-bit operands only (fp8=True is a dat configuration)")
         self.mode = mode
-        super().__init__(params, tasks, device, batch, res, fp8=False, **kw)
+        super().__init__(params, tasks, device, batch, res, **kw)
         self._init_vectors(params)
 
     @_bound
     def _init_vectors(self, params):
         dev, H, I, R, B, nl = self.dev, self.H, self.I, self.R, self.B, self.nl
         bias = self.mode == "bias"
-        self.opt_adapters = ()
         self.loss_out = torch.zeros(4, device=dev)
         # ---------------- the trainable vectors: one flat group, the kernels' frozen entries become views into it
         self.vec = FlatGroup(vector_names(self.mode, nl, H, I), dev, True)
@@ -113,15 +109,11 @@ class ViltVectorEngine(ViltDatEngine):
             self.pool_b = v(ENC + "pooler.dense.bias")
         else:
             self.lnf_g = v(ENC + "layernorm.weight")
-        # ---------------- activations kept for the backward: every layer below the top one at R rows, layer 0 included
-        u0 = torch.empty(R, I, dtype=torch.uint8, device=dev) if self.g8u else torch.empty(R, I, dtype=self.op_dtype, device=dev)
-        l0 = self.l0
-        a0 = dict(h_in=self.h0, st1=torch.empty(R, 2, device=dev), qkv=l0["qkv"], ctx=l0["ctx"], lse=l0["lse"], h2=l0["h2"],
-                  st2=torch.empty(R, 2, device=dev), u=u0, h3=l0["h3"])
-        self.actv = [a0] + [self.act[i] for i in range(1, nl)]
-        for i in range(1, nl):      # no adapter between the layers: layer i reads layer i - 1's output in place
-            self.actv[i]["h_in"] = self.actv[i - 1]["h3"]
-        self.act = [None] * nl      # (the dat engine's per-layer h_in buffers are not used here)
+        # ---------------- activations kept for the backward: every layer at R rows, layer 0 included; no adapter between the
+        # layers, so layer i reads layer i - 1's output in place
+        self.act: List[dict] = []
+        for i in range(nl):
+            self.act.append(self._kept_layer(h_in=self.h0 if i == 0 else self.act[i - 1]["h3"]))
         # static row masks of h0's [text | cls | patches] rows
         s = torch.arange(self.S, device=dev).repeat(B)
         self.text_rows = (s < self.Lt).to(torch.uint8).contiguous()
@@ -184,20 +176,15 @@ class ViltVectorEngine(ViltDatEngine):
         self._embed()
         top = self.nl - 1
         for i in range(top):
-            a = self.actv[i]
+            a = self.act[i]
             self._layer_body(i, a["h_in"], R, B, a["qkv"], a["ctx"], a["lse"], a["h2"], a["h3"], st1=a["st1"], st2=a["st2"],
                              u=a["u"], mask=m1, ln1_done=False)
-        a, W, t = self.actv[top], self.layers[top], self.top
-        ws = self._skinny_ws()
+        a, W, t = self.act[top], self.layers[top], self.top
         x16 = self.x16[:R]
         L.layernorm_fwd(a["h_in"], W["ln1g"], W["ln1b"], self.ln_eps, R, H, y_bf16=x16, stats=a["st1"])
         L.gemm_bf16_nt(x16, W["wqkv"], L.EPI_BF16, bias=W["bqkv"], out_bf16=a["qkv"])
         L.attn_cls_fwd(a["qkv"], a["ctx"], a["lse"], B, self.S, self.heads, key_mask=m1)
-        L.gemm_bf16_nt(self._cls_rows(a["ctx"], B), W["wo"], L.EPI_RESID_F32, bias=W["bo"], resid=self._cls_rows(a["h_in"], B),
-                       out_f32=t["h2"], skinny_workspace=ws)
-        L.layernorm_fwd(t["h2"], W["ln2g"], W["ln2b"], self.ln_eps, B, H, y_bf16=t["x16"], stats=t["st2"])
-        L.gemm_bf16_nt(t["x16"], W["w1"], L.EPI_GELU, bias=W["b1"], out_bf16=t["f16"], out2_bf16=t["u"], skinny_workspace=ws)
-        L.gemm_bf16_nt(t["f16"], W["w2"], L.EPI_RESID_F32, bias=W["b2"], resid=t["h2"], out_f32=t["h3"], skinny_workspace=ws)
+        self._top_token0_fwd(a, W, B)
         self._pool(t["h3"], B, x_stride=H)
 
     # ------------------------------------------------------------------------------------------ backward
@@ -207,7 +194,7 @@ class ViltVectorEngine(ViltDatEngine):
         bias = self.mode == "bias"
         m1 = self.key_mask2[:B]
         top = self.nl - 1
-        a, W, t = self.actv[top], self.layers[top], self.top
+        a, W, t = self.act[top], self.layers[top], self.top
         ws = self._skinny_ws()
         if bias:      # the pooler's pre-tanh gradient (the loss scale enters below it)
             L.tanh_bwd(self.pooled[:B], self.dpooled[:B], self.dpre[:B])
@@ -243,7 +230,7 @@ class ViltVectorEngine(ViltDatEngine):
             L.layernorm_bwd_dx(a["h_in"], a["st1"], W["ln1g"], R, H, dy_bf16=dx16, dres=t["dh2"], dres_every=self.S, out_f32=cur)
         # ---- layers L-2 .. 0 at R rows; `cur` = gradient of the residual stream leaving layer i
         for i in range(top - 1, -1, -1):
-            a, W = self.actv[i], self.layers[i]
+            a, W = self.act[i], self.layers[i]
             if bias:
                 self._colsum((i, "b2"), cur)
             L.cvt_f32_bf16(cur, dh16)
@@ -326,8 +313,5 @@ class ViltVectorEngine(ViltDatEngine):
         reference's communicated list too, but get_average_net skips every 'clf' key: main.py:54)."""
         return self.vec.p
 
-    def repack_adapter(self, a: int):
-        """Nothing to repack: the kernels read the fp32 vectors in place."""
-
-    def repack(self):
-        """Nothing to repack (after a load / FedAvg write-back)."""
+    def comm_written(self):
+        """Nothing to rebuild: the kernels read the fp32 vectors in place."""

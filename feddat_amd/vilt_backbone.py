@@ -1,0 +1,405 @@
+"""The frozen ViLT-B/32 backbone and the task head, as every ViLT local-update engine uses them on MI355X.
+
+What the dual-adapter engine (engine.ViltDatEngine), the single-adapter engine (adapter_engine.ViltAdapterEngine) and the bias /
+LayerNorm-only engine (vector_engine.ViltVectorEngine) share INSIDE a train_step: the geometry, the frozen weights as 16-bit MFMA
+operands (+ transposes for the dX products), the task heads, the static input buffers, the embeddings, the body of one HF ViltLayer,
+the token-0 block of the top layer, LayerNorm + pooler, the head's forward / backward, and the workspace all of this runs on.
+What they share AROUND the step is local_update.LocalUpdateEngine.  An engine derived from ViltBackbone adds its own trainable
+groups, says which layers' activations it keeps (_kept_layer), and sequences its own forward, backward and step.
+
+No arithmetic happens in Python/PyTorch here: torch only owns the device buffers and the stream; every launch goes through the C ABI,
+on static buffers, so a whole train_step can be captured into one hipGraph (torch.cuda.CUDAGraph stream capture) and replayed.
+"""
+from __future__ import annotations
+
+import math
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import torch
+
+from . import lib as L
+from .local_update import FlatGroup, LocalUpdateEngine, _bound
+
+ENC = "vilt_encoder.vilt."
+HEAD_TENSORS = ("clf_fc0.weight", "clf_fc0.bias", "clf_norm0.weight", "clf_norm0.bias", "clf_fc1.weight",
+                "clf_fc1.bias")
+
+
+class ViltBackbone(LocalUpdateEngine):
+    # passes per sample batched through the backbone: sizes the shared workspace (NPASS * B samples, NPASS * R rows)
+    NPASS = 1
+    # state-dict stem of the FFN's second product: the plain HF ViltOutput key
+    FFN2_STEM = "output.dense."
+
+    def __init__(self, params: Dict[str, torch.Tensor], tasks: Sequence[str], device, batch: int, res: int,
+                 text_len: int = 40, layers: int = 12, num_labels: int = 100, lr: float = 1e-4,
+                 weight_decay: float = 1e-2, adam_eps: float = 1e-8, gelu_codes: bool = True, operands: Optional[str] = None,
+                 loss_scale: Optional[float] = None, dynamic_loss_scale: Optional[bool] = None,
+                 scale_growth_interval: int = 2000):
+        """operands ("f16", the default, or "bf16"), loss_scale, dynamic_loss_scale, scale_growth_interval and gelu_codes: see
+        engine.ViltDatEngine."""
+        self._init_loss_scale(operands or "f16", loss_scale, dynamic_loss_scale, scale_growth_interval)
+        self._init_backbone(params, tasks, device, batch, res, text_len, layers, num_labels, lr, weight_decay, adam_eps,
+                            gelu_codes)
+
+    def _param(self, params, name):
+        return params[name].to(self.dev, torch.float32).contiguous()
+
+    def _f32(self, *s):
+        return torch.empty(*s, device=self.dev)
+
+    def _b16(self, *s):
+        return torch.empty(*s, dtype=self.op_dtype, device=self.dev)
+
+    @_bound
+    def _init_backbone(self, params, tasks, device, batch, res, text_len, layers, num_labels, lr, weight_decay, adam_eps,
+                       gelu_codes):
+        L.load()
+        self.dev = torch.device(device)
+        self.tasks = list(tasks)
+        self.B, self.Lt, self.nl = batch, text_len, layers
+        self.res = (res, res) if isinstance(res, int) else tuple(res)      # (height, width), multiples of 32
+        self.H, self.I, self.heads, self.C = 768, 3072, 12, num_labels
+        self.P = 32
+        self.gh, self.gw = self.res[0] // self.P, self.res[1] // self.P
+        self.np = self.gh * self.gw
+        self.S = text_len + 1 + self.np
+        self.R = batch * self.S
+        self.lr, self.wd, self.eps = lr, weight_decay, adam_eps
+        self.ln_eps = 1e-12
+        dev = self.dev
+        H, I = self.H, self.I
+
+        def P(name):
+            return self._param(params, name)
+
+        def bf16_of(w):
+            out = torch.empty(w.shape, dtype=self.op_dtype, device=dev)
+            L.cvt_f32_bf16(w, out)
+            return out
+
+        def bf16_T(w):  # [R,C] fp32 -> [C,R] bf16
+            out = torch.empty(w.shape[1], w.shape[0], dtype=self.op_dtype, device=dev)
+            L.transpose_f32_bf16(w, out, w.shape[0], w.shape[1])
+            return out
+
+        # ---------------- frozen backbone (bf16 weights + their transposes for the dX products) --------------
+        e = ENC + "embeddings."
+        self.emb = {k: P(e + k) for k in (
+            "text_embeddings.word_embeddings.weight", "text_embeddings.position_embeddings.weight",
+            "text_embeddings.token_type_embeddings.weight", "text_embeddings.LayerNorm.weight",
+            "text_embeddings.LayerNorm.bias", "patch_embeddings.projection.bias")}
+        tok = P(e + "token_type_embeddings.weight")
+        self.mod0, self.mod1 = tok[0].contiguous(), tok[1].contiguous()
+        self.cls = P(e + "cls_token").reshape(H).contiguous()
+        pos = P(e + "position_embeddings")[0]
+        self.pos0 = pos[0].contiguous()
+        # per-sample position grids: the 12 x 12 table resized to each sample's valid patch rectangle (pixel_mask)
+        self.pos_grid = pos[1:].contiguous()
+        self.g0 = int(round(math.sqrt(pos.shape[0] - 1)))
+        self.pos_img = torch.empty(batch, self.np, H, device=dev)
+        self.w_patch = bf16_of(P(e + "patch_embeddings.projection.weight").reshape(H, 3 * self.P * self.P))
+        self.layers: List[dict] = []
+        for i in range(layers):
+            Lp = ENC + f"encoder.layer.{i}."
+            wq, wk, wv = (P(Lp + f"attention.attention.{n}.weight") for n in ("query", "key", "value"))
+            wqkv = torch.cat([wq, wk, wv], 0).contiguous()
+            bqkv = torch.cat([P(Lp + f"attention.attention.{n}.bias") for n in ("query", "key", "value")]).contiguous()
+            wo, w1, w2 = P(Lp + "attention.output.dense.weight"), P(Lp + "intermediate.dense.weight"), \
+                P(Lp + self.FFN2_STEM + "weight")
+            self.layers.append(dict(
+                wqkv=bf16_of(wqkv), wqkvT=bf16_T(wqkv), bqkv=bqkv,
+                wo=bf16_of(wo), woT=bf16_T(wo), bo=P(Lp + "attention.output.dense.bias"),
+                w1=bf16_of(w1), w1T=bf16_T(w1), b1=P(Lp + "intermediate.dense.bias"),
+                w2=bf16_of(w2), w2T=bf16_T(w2), b2=P(Lp + self.FFN2_STEM + "bias"),
+                ln1g=P(Lp + "layernorm_before.weight"), ln1b=P(Lp + "layernorm_before.bias"),
+                ln2g=P(Lp + "layernorm_after.weight"), ln2b=P(Lp + "layernorm_after.bias")))
+        self.lnf_g, self.lnf_b = P(ENC + "layernorm.weight"), P(ENC + "layernorm.bias")
+        self.pool_w, self.pool_b = P(ENC + "pooler.dense.weight"), P(ENC + "pooler.dense.bias")
+
+        # ---------------- trainable state every engine has: one head per task (an engine's adapters, if any, go into self.ad) ----
+        self.ad: List[FlatGroup] = []
+        self.opt_adapters: Tuple[int, ...] = ()
+        head_shapes = {"clf_fc0.weight": (2 * H, H), "clf_fc0.bias": (2 * H,), "clf_norm0.weight": (2 * H,),
+                       "clf_norm0.bias": (2 * H,), "clf_fc1.weight": (num_labels, 2 * H), "clf_fc1.bias": (num_labels,)}
+        self.head = {t: FlatGroup([(f"task_layer.{t}.{n}", head_shapes[n]) for n in HEAD_TENSORS], dev, True)
+                     for t in self.tasks}
+        for grp in self.head.values():
+            for n in grp.names:
+                grp.view(n).copy_(params[n].to(dev, torch.float32))
+
+        # ---------------- workspace (static: a whole step is graph-capturable) ----------------
+        R, R2, B = self.R, self.NPASS * self.R, batch
+        f32, b16 = self._f32, self._b16
+        self._px_shape = (B, 3, self.res[0], self.res[1])
+        self.inp = dict(input_ids=torch.zeros(B, text_len, dtype=torch.int64, device=dev),
+                        token_type_ids=torch.zeros(B, text_len, dtype=torch.int64, device=dev),
+                        target=f32(B, num_labels),
+                        attention_mask=torch.ones(B, text_len, dtype=torch.int64, device=dev),
+                        # pixel_mask sampled at the patch origins (all that HF's visual_embed looks at): [B, gh, gw]
+                        patch_mask=torch.ones(B, self.gh, self.gw, dtype=torch.int64, device=dev))
+        # attention key masks of the [text | CLS | patches] sequence, derived on the device from the two HF masks
+        # inside the step (no host sync, valid for every batch under one captured graph); rows [B, 2B) repeat [0, B)
+        self.key_mask2 = torch.ones(self.NPASS * B, self.S, dtype=torch.uint8, device=dev)
+        self.patches = b16(B * self.np, 3 * self.P * self.P)
+        self.proj = f32(B * self.np, H)
+        self.h0 = f32(R, H)
+        self.x16 = b16(R2, H)          # LN output (GEMM operand), transient
+        self.f16 = b16(R2, I)          # gelu(u), transient
+        # what FFN2^T needs of the pre-GELU u: 8-bit gelu'(u) codes where the persistent GEMM applies (FEDDAT_EPI_GELU_G8 /
+        # _MUL_G8, M >= 1024: 25 % fewer bytes through the two HBM-bound epilogues), else u itself in bf16
+        self.g8u = R2 >= 1024 and bool(gelu_codes)
+        # top layer: only token 0 of each sample feeds the pooler, so everything after its attention runs on NPASS * B rows
+        nb2 = self.NPASS * B
+        self.top = dict(h2=f32(nb2, H), st2=f32(nb2, 2), u=b16(nb2, I), h3=f32(nb2, H), x16=b16(nb2, H),
+                        f16=b16(nb2, I), dh316=b16(nb2, H), dU=b16(nb2, I), dx2=b16(nb2, H), dh2=f32(nb2, H),
+                        dh216=b16(nb2, H), dctx=f32(nb2, H))
+        # head / pooler
+        self.cls_ln = f32(2 * B, H)
+        self.cls_st = f32(2 * B, 2)
+        self.pooled = f32(2 * B, H)
+        # task-head activations: "both" = a 2B-row pass, "all" = its rows [0,B), "p1" = its rows [B,2B)
+        both = dict(a0=f32(2 * B, 2 * H), n0=f32(2 * B, 2 * H), st=f32(2 * B, 2), g0=f32(2 * B, 2 * H),
+                    logits=f32(2 * B, num_labels))
+        self.hd = {"both": both, "all": {k: v[:B] for k, v in both.items()}, "p1": {k: v[B:] for k, v in both.items()}}
+        self.dlogits = f32(B, num_labels)
+        self.dg0, self.dn0, self.da0 = f32(B, 2 * H), f32(B, 2 * H), f32(B, 2 * H)
+        self.dpooled = f32(2 * B, H)
+        self.dpre = f32(2 * B, H)
+        self.dcls_ln = f32(2 * B, H)
+        self.dcls = f32(2 * B, H)
+        # backward streams
+        self.dh = [f32(R2, H), f32(R2, H)]       # ping-pong residual-gradient stream
+        self.dh16 = b16(R2, H)
+        self.dU = b16(R2, I)
+        self.dx16 = b16(R2, H)
+        self.dctx = b16(R2, H)
+        self.dqkv = b16(R2, 3 * H)
+        self.graph = None
+        self.ctx = L.Context(self.dev.index if self.dev.index is not None else torch.cuda.current_device())
+        # True: the serial tail (token-0 LayerNorm + pooler, task head forward / backward, loss, optimizer bookkeeping) on the
+        # fused kernels of csrc/head_tail.hip (20 launches); False: the round-3 sequence of 46 single-purpose launches (same
+        # arithmetic up to fp32 summation order; tools/step_breakdown.py --unfused-tail, and the tests compare the two)
+        self.fused_tail = True
+        # True: the last layer's attention computes the ONE query per (sample, head) the pooler consumes (token 0) and its
+        # rank-1 backward (feddat_attn_cls_fwd / _bwd); False: the dense kernels on all S queries (184 of 185 never read)
+        self.cls_attention = True
+        self.sched = dict(warmup=1, total=2)
+        self.task = self.tasks[0]
+        # dynamic loss scale (GradScaler on the device)
+        self._alloc_scaler()
+
+    def _kept_layer(self, h_in=None):
+        """The buffers of ONE layer's activations that its backward reads, NPASS * R rows each.  h_in: the layer's input where it
+        already lives somewhere (the previous layer's h3); None: a buffer of the layer's own.  FFN2^T needs of the pre-GELU u
+        only what self.g8u says: the 8-bit gelu' codes, else u itself in 16 bits."""
+        R2, H, I = self.NPASS * self.R, self.H, self.I
+        f32, b16 = self._f32, self._b16
+        return dict(h_in=f32(R2, H) if h_in is None else h_in, st1=f32(R2, 2), qkv=b16(R2, 3 * H), ctx=b16(R2, H),
+                    lse=f32(self.NPASS * self.B, self.heads, self.S), h2=f32(R2, H), st2=f32(R2, 2),
+                    u=torch.empty(R2, I, dtype=torch.uint8, device=self.dev) if self.g8u else b16(R2, I), h3=f32(R2, H))
+
+    # ------------------------------------------------------------------------------------------ inputs
+    @_bound
+    def set_batch(self, batch: Dict[str, torch.Tensor]):
+        """Copy one batch (reference schema: HF ViLT encodings + target_scores) into the static input buffers."""
+        px = batch["pixel_values"]
+        if tuple(px.shape) != self._px_shape:
+            raise L.FeddatHipError(f"engine built for pixel_values {self._px_shape}, got {tuple(px.shape)}")
+        # the pixels are consumed right here, from the caller's tensor: patch extraction (im2col + bf16) is the only reader of
+        # pixel_values, so it runs ahead of the captured step instead of a 57 MB device-to-device copy into a static buffer
+        # followed by the same read inside the graph (stream-ordered with the replay that follows)
+        if not px.is_cuda:
+            px = px.to(self.dev, non_blocking=True)
+        L.im2col_patches(px.to(torch.float32).contiguous(), self.patches, self.B, 3, self.res[0], self.res[1], self.P)
+        ids, tts, am, tg, pm = (batch.get(k) for k in ("input_ids", "token_type_ids", "attention_mask", "target_scores",
+                                                        "pixel_mask"))
+
+        def dev_ok(t, dt, shape):
+            return t is None or (t.is_cuda and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == shape)
+        B, Lt = self.B, self.Lt
+        if (ids is not None and tts is not None and dev_ok(ids, torch.int64, (B, Lt)) and dev_ok(tts, torch.int64, (B, Lt))
+                and dev_ok(am, torch.int64, (B, Lt)) and dev_ok(tg, torch.float32, (B, self.C))
+                and dev_ok(pm, torch.int64, (B, self.res[0], self.res[1]))):
+            # the usual case (device-resident batch in the reference's dtypes): one launch for all five
+            L.vilt_stage_inputs(ids, tts, am, tg, pm, self.inp, B, Lt, self.C, self.res[0], self.res[1], self.P)
+            return
+        self.inp["input_ids"].copy_(batch["input_ids"], non_blocking=True)
+        self.inp["token_type_ids"].copy_(batch["token_type_ids"], non_blocking=True)
+        if "target_scores" in batch:
+            self.inp["target"].copy_(batch["target_scores"], non_blocking=True)
+        if batch.get("attention_mask") is not None:     # absent = all valid
+            self.inp["attention_mask"].copy_(batch["attention_mask"], non_blocking=True)
+        else:
+            self.inp["attention_mask"].fill_(1)
+        if batch.get("pixel_mask") is not None:
+            self.inp["patch_mask"].copy_(batch["pixel_mask"][:, ::self.P, ::self.P], non_blocking=True)
+        else:
+            self.inp["patch_mask"].fill_(1)
+
+    # ------------------------------------------------------------------------------------------ forward
+    def _embed(self):
+        B, H, S, Lt = self.B, self.H, self.S, self.Lt
+        e = self.emb
+        L.text_embed(self.inp["input_ids"], self.inp["token_type_ids"], e["text_embeddings.word_embeddings.weight"],
+                     e["text_embeddings.position_embeddings.weight"], e["text_embeddings.token_type_embeddings.weight"],
+                     e["text_embeddings.LayerNorm.weight"], e["text_embeddings.LayerNorm.bias"], self.ln_eps,
+                     self.mod0, self.h0, B, Lt, S, H)
+        # (self.patches was filled by set_batch: im2col of the caller's pixel_values)
+        L.gemm_bf16_nt(self.patches, self.w_patch, L.EPI_F32, bias=e["patch_embeddings.projection.bias"],
+                       out_f32=self.proj)
+        if self.fused_tail:      # key mask + per-sample position grid + assembly in one launch (bit-identical)
+            L.image_embed_assemble_masked(self.proj, self.cls, self.pos0, self.pos_grid, self.inp["patch_mask"],
+                                          self.inp["attention_mask"], self.mod1, self.h0, self.key_mask2, B, Lt, self.gh,
+                                          self.gw, self.g0, H, nrep=self.NPASS)
+            return
+        L.vilt_key_mask(self.inp["attention_mask"], self.inp["patch_mask"], self.key_mask2, B, Lt, self.gh, self.gw, 1,
+                        nrep=self.NPASS)
+        L.pos_embed_resize_masked(self.pos_grid, self.inp["patch_mask"], self.pos_img, self.g0, B, self.gh, self.gw, 1,
+                                  H)
+        L.image_embed_assemble(self.proj, self.cls, self.pos0, self.pos_img, self.mod1, self.h0, B, Lt, self.np, S, H,
+                               pos_batch_stride=self.np * H)
+
+    def _layer_body(self, i: int, h_in, rows: int, nb: int, qkv, ctx, lse, h2, h3, st1=None, st2=None, u=None,
+                    mask=None, ln1_done=False):
+        """LN -> QKV -> attention -> out-proj(+res) -> LN -> FFN1(gelu) -> FFN2(+res): HF ViltLayer (with an adapter behind it,
+        the Adaptered_ViltOutput dense+residual: adaptered_output.py:74-76, and h3 is the adapter's input)."""
+        W, H = self.layers[i], self.H
+        x16, f16 = self.x16[:rows], self.f16[:rows]
+        g8 = u is not None and u.dtype == torch.uint8
+        if not ln1_done:     # otherwise x16 / st1 were written by the previous layer's fused adapter + LN kernel
+            L.layernorm_fwd(h_in, W["ln1g"], W["ln1b"], self.ln_eps, rows, H, y_bf16=x16, stats=st1)
+        L.gemm_bf16_nt(x16, W["wqkv"], L.EPI_BF16, bias=W["bqkv"], out_bf16=qkv)
+        L.attn_fwd(qkv, ctx, lse, nb, self.S, self.heads, key_mask=mask)
+        L.gemm_bf16_nt(ctx, W["wo"], L.EPI_RESID_F32, bias=W["bo"], resid=h_in, out_f32=h2)
+        L.layernorm_fwd(h2, W["ln2g"], W["ln2b"], self.ln_eps, rows, H, y_bf16=x16, stats=st2)
+        L.gemm_bf16_nt(x16, W["w1"], L.EPI_GELU_G8 if g8 else L.EPI_GELU, bias=W["b1"], out_bf16=f16, out2_bf16=u)
+        L.gemm_bf16_nt(f16, W["w2"], L.EPI_RESID_F32, bias=W["b2"], resid=h2, out_f32=h3)
+
+    def _sg(self, A, sa_i, sa_k, Bm, sb_k, sb_j, I, J, K, out, ksplit=1, bias_j=None, alpha=1.0):
+        """Skinny exact-fp32 product; long contractions are split over the grid and reduced deterministically."""
+        if ksplit <= 1:
+            L.sgemm_f32(A, sa_i, sa_k, Bm, sb_k, sb_j, I, J, K, out, bias_j=bias_j, alpha=alpha)
+            return
+        part = self._scratch1(ksplit * I * J)
+        L.sgemm_f32(A, sa_i, sa_k, Bm, sb_k, sb_j, I, J, K, part, ksplit=ksplit, bias_j=bias_j,
+                    out_split_stride=I * J, alpha=alpha)
+        L.reduce_partials(part, I * J, ksplit, I * J, out)
+
+    def _scratch1(self, n):
+        if not hasattr(self, "_scr") or self._scr.numel() < n:
+            self._scr = torch.empty(n, device=self.dev)
+        return self._scr
+
+    def _cls_rows(self, t, nb: int):
+        """Strided view of token 0 of every sample: [nb, width] with row stride S * width (no copy)."""
+        w = t.shape[1]
+        return t.view(nb, self.S * w)[:, :w]
+
+    def _top_token0_fwd(self, a, W, nb: int):
+        """The top layer behind its attention, on the nb token-0 rows (only token 0 of each sample reaches the pooler: HF
+        ViltPooler takes hidden_states[:, 0]; vilt.py:127), read in place through strided GEMM operands: attention-output
+        projection (+ residual), LN2, FFN1 + GELU, FFN2 (+ residual) -> self.top["h3"]."""
+        H, t = self.H, self.top
+        L.gemm_bf16_nt(self._cls_rows(a["ctx"], nb), W["wo"], L.EPI_RESID_F32, bias=W["bo"],
+                       resid=self._cls_rows(a["h_in"], nb), out_f32=t["h2"], skinny_workspace=self._skinny_ws())
+        L.layernorm_fwd(t["h2"], W["ln2g"], W["ln2b"], self.ln_eps, nb, H, y_bf16=t["x16"], stats=t["st2"])
+        L.gemm_bf16_nt(t["x16"], W["w1"], L.EPI_GELU, bias=W["b1"], out_bf16=t["f16"], out2_bf16=t["u"],
+                       skinny_workspace=self._skinny_ws())
+        L.gemm_bf16_nt(t["f16"], W["w2"], L.EPI_RESID_F32, bias=W["b2"], resid=t["h2"], out_f32=t["h3"],
+                       skinny_workspace=self._skinny_ws())
+
+    def _skinny_ws(self):
+        """fp32 split-K partials of the top layer's 2B-row GEMMs (largest: 2B x 3072 x 768)."""
+        if getattr(self, "_skws", None) is None:
+            nb, H, I = self.NPASS * self.B, self.H, self.I
+            n = max(L.gemm_skinny_workspace_elems(nb, I, H), L.gemm_skinny_workspace_elems(nb, H, I),
+                    L.gemm_skinny_workspace_elems(nb, H, H), L.gemm_skinny_workspace_elems(nb, H, 3 * H)) if nb <= 64 else 0
+            self._skws = torch.empty(max(n, 1), device=self.dev) if n else False
+        return self._skws if self._skws is not False else None
+
+    def _pool(self, h_last, nb: int, x_stride: int = None):
+        """ViltModel.layernorm on token 0 + ViltPooler (dense + tanh) -> self.pooled[:nb]."""
+        H = self.H
+        self._pool_src, self._pool_stride = h_last, (self.S * H if x_stride is None else x_stride)
+        if self.fused_tail:      # LayerNorm (statistics in the block) -> dense -> tanh in one launch
+            L.head_gemm(L.ht_job(h_last, self._pool_stride, 1, self.pool_w, 1, H, nb, H, H, self.pooled, bias_j=self.pool_b,
+                                 pro=L.HT_PRO_LN, pro_a=self.lnf_g, pro_b=self.lnf_b, pro_eps=self.ln_eps,
+                                 stats_out=self.cls_st, epi=L.HT_EPI_TANH))
+            return
+        L.layernorm_fwd(h_last, self.lnf_g, self.lnf_b, self.ln_eps, nb, H, x_stride=self._pool_stride,
+                        y_f32=self.cls_ln, stats=self.cls_st)
+        self._sg(self.cls_ln, H, 1, self.pool_w, 1, H, nb, H, H, self.pooled, ksplit=4, bias_j=self.pool_b)
+        L.tanh_fwd(self.pooled[:nb])
+
+    def _head_fwd(self, pooled, slot: str, task: str):
+        """vilt.py:202-209: fc0 -> LayerNorm(1536, eps 1e-5) -> GELU -> fc1 on the rows of `pooled` (B, or 2B for the
+        joint P0 + P1 pass)."""
+        B, H, C = pooled.shape[0], self.H, self.C
+        hp, s = self.head[task], self.hd[slot]
+        pre = f"task_layer.{task}."
+        if self.fused_tail:
+            L.head_gemm(L.ht_job(pooled, H, 1, hp.view(pre + "clf_fc0.weight"), 1, H, B, 2 * H, H, s["a0"],
+                                 bias_j=hp.view(pre + "clf_fc0.bias")))
+            L.head_ln_gelu(s["a0"], hp.view(pre + "clf_norm0.weight"), hp.view(pre + "clf_norm0.bias"), 1e-5, s["n0"], s["st"],
+                           s["g0"])
+            L.head_gemm(L.ht_job(s["g0"], 2 * H, 1, hp.view(pre + "clf_fc1.weight"), 1, 2 * H, B, C, 2 * H, s["logits"],
+                                 bias_j=hp.view(pre + "clf_fc1.bias")))
+            return s["logits"]
+        self._sg(pooled, H, 1, hp.view(pre + "clf_fc0.weight"), 1, H, B, 2 * H, H, s["a0"], ksplit=4,
+                 bias_j=hp.view(pre + "clf_fc0.bias"))
+        L.layernorm_fwd(s["a0"], hp.view(pre + "clf_norm0.weight"), hp.view(pre + "clf_norm0.bias"), 1e-5, B, 2 * H,
+                        y_f32=s["n0"], stats=s["st"])
+        L.gelu_fwd(s["n0"], s["g0"])
+        self._sg(s["g0"], 2 * H, 1, hp.view(pre + "clf_fc1.weight"), 1, 2 * H, B, C, 2 * H, s["logits"], ksplit=16,
+                 bias_j=hp.view(pre + "clf_fc1.bias"))
+        return s["logits"]
+
+    def _head_bwd(self, pooled, slot: str, task: str, dpooled_out):
+        """Gradients of the task head (all six tensors, fp32) and d(pooled) for B rows."""
+        B, H, C = self.B, self.H, self.C
+        hp, s = self.head[task], self.hd[slot]
+        pre = f"task_layer.{task}."
+
+        def G(n):
+            return hp.view(pre + n, hp.g)
+        dl = self.dlogits
+        if self.fused_tail:
+            # {dW_fc1 = dl^T g0, db_fc1} next to {dn0 = (dl W_fc1) * gelu'(n0)}; LayerNorm backward (dx, dgamma, dbeta);
+            # {dW_fc0 = da0^T pooled, db_fc0} next to {dpooled = da0 W_fc0}: three launches
+            L.head_gemm(L.ht_job(dl, 1, C, s["g0"], 2 * H, 1, C, 2 * H, B, G("clf_fc1.weight"), mode=1, colsum=G("clf_fc1.bias")),
+                        L.ht_job(dl, C, 1, hp.view(pre + "clf_fc1.weight"), 2 * H, 1, B, 2 * H, C, self.dn0,
+                                 epi=L.HT_EPI_MUL_DGELU, aux=s["n0"], ld_aux=2 * H))
+            L.head_ln_bwd_full(self.dn0, s["a0"], s["st"], hp.view(pre + "clf_norm0.weight"), self.da0, G("clf_norm0.weight"),
+                               G("clf_norm0.bias"))
+            L.head_gemm(L.ht_job(self.da0, 1, 2 * H, pooled, H, 1, 2 * H, H, B, G("clf_fc0.weight"), mode=1,
+                                 colsum=G("clf_fc0.bias")),
+                        L.ht_job(self.da0, 2 * H, 1, hp.view(pre + "clf_fc0.weight"), H, 1, B, H, 2 * H, dpooled_out))
+            return
+        L.sgemm_f32(dl, 1, C, s["g0"], 2 * H, 1, C, 2 * H, B, G("clf_fc1.weight"), colsum=G("clf_fc1.bias"))
+        L.sgemm_f32(dl, C, 1, hp.view(pre + "clf_fc1.weight"), 2 * H, 1, B, 2 * H, C, self.dg0)
+        L.gelu_bwd(s["n0"], self.dg0, self.dn0)
+        L.layernorm_bwd_full(self.dn0, s["a0"], s["st"], hp.view(pre + "clf_norm0.weight"), B, 2 * H, self.da0,
+                             G("clf_norm0.weight"), G("clf_norm0.bias"))
+        L.sgemm_f32(self.da0, 1, 2 * H, pooled, H, 1, 2 * H, H, B, G("clf_fc0.weight"), colsum=G("clf_fc0.bias"))
+        self._sg(self.da0, 2 * H, 1, hp.view(pre + "clf_fc0.weight"), H, 1, B, H, 2 * H, dpooled_out, ksplit=8)
+
+    def _adamw(self, grp: FlatGroup):
+        """One group's AdamW as its own launch (the unfused tail)."""
+        L.adamw_flat(grp.p, grp.g, grp.m, grp.v, grp.seg_off, self._wd_vec(grp), grp.state, self.lr,
+                     self.sched["warmup"], self.sched["total"], 0.9, 0.98, self.eps)
+
+    def _dyn(self) -> bool:
+        """Dynamic loss scale in effect (it rides on the fused tail's multi-group AdamW launch)."""
+        return self.dynamic_scale and self.fused_tail
+
+    def _scale_in(self):
+        """How the loss scale enters the backbone's backward (factor of the pooler-backward product); it leaves through
+        _scale_out."""
+        return dict(alpha=1.0, alpha_dev=self.scaler_f[0:1]) if self._dyn() else dict(alpha=self.loss_scale)
+
+    def _graph_switches(self) -> Tuple:
+        return (self.task, self.fused_tail, self.cls_attention)
+
+    def _state_groups(self):
+        return self.ad + list(self.head.values())

@@ -117,3 +117,41 @@ def test_main_refuses_albef_adapter_and_other_modes():
         train.main(["--encoder_name", "albef_no_distill", "--optimizer_mode", "adapter"])
     with pytest.raises(L.FeddatHipError):
         train.main(["--optimizer_mode", "lora"])
+
+
+def test_allreduce_average_tells_the_engine_through_comm_written(tmp_path, monkeypatch):
+    """fedavg.allreduce_average on an engine whose averaged adapter is slot 0 (ViltAdapterEngine.COMM_ADAPTER): after the write-back
+    it calls the engine's comm_written() once, whose default rebuilds the operand copies of slot COMM_ADAPTER -- never slot 1.
+    One-rank gloo group, the HIP pre-scale replaced by test_fedavg_gloo's host stand-in (same operation order)."""
+    import torch.distributed as dist
+    from feddat_amd import fedavg
+    from feddat_amd.local_update import LocalUpdateEngine
+
+    class Stub(LocalUpdateEngine):
+        COMM_ADAPTER = 0
+
+        def __init__(self):
+            self.flat = torch.randn(4096, generator=torch.Generator().manual_seed(3))
+            self.written, self.repacked = 0, []
+
+        def comm_flat(self):
+            return self.flat
+
+        def comm_written(self):
+            self.written += 1
+            super().comm_written()
+
+        def repack_adapter(self, a):
+            self.repacked.append(a)
+
+    monkeypatch.setattr(fedavg.L, "fedavg_accumulate", lambda acc, x, num, total, first: acc.copy_(x * num / total))
+    eng = Stub()
+    sent = eng.flat.clone()
+    dist.init_process_group("gloo", init_method=f"file://{tmp_path}/rendezvous", rank=0, world_size=1)
+    try:
+        out = fedavg.allreduce_average(eng, 1)
+    finally:
+        dist.destroy_process_group()
+    assert out is eng.flat and torch.equal(eng.flat, sent)
+    assert eng.written == 1
+    assert eng.repacked == [0]

@@ -137,3 +137,11 @@ def test_engine_refuses_fp8_and_unknown_modes():
         ViltVectorEngine({}, ["art"], "cpu", 2, 224, mode="bias", fp8=True)
     with pytest.raises(L.FeddatHipError):
         ViltVectorEngine({}, ["art"], "cpu", 2, 224, mode="lora")
+
+
+def test_vector_engine_is_a_backbone_and_not_a_dat_engine():
+    from feddat_amd.engine import ViltDatEngine
+    from feddat_amd.vector_engine import ViltVectorEngine
+    from feddat_amd.vilt_backbone import ViltBackbone
+    assert issubclass(ViltVectorEngine, ViltBackbone) and issubclass(ViltDatEngine, ViltBackbone)
+    assert not issubclass(ViltVectorEngine, ViltDatEngine)

@@ -1,25 +1,40 @@
 #!/usr/bin/env python
-"""Hash of the trained state (adapter_0, adapter_1, head) of the full ViLT-B/32 engine after 12 hipGraph-replayed train_steps at
-configs[1]'s size, default settings.  Two builds with the same hash run the same arithmetic: at 80 steps the AdamW trajectory is
-chaotic enough that a last-bit change moves the round-length parity draws ("draws"), so a kernel change meant
-to be arithmetic-neutral is checked with this before the 80-step tests are trusted.  python tools/state_hash.py [repo root]
-round 6 HEAD (= round 5's arithmetic): cb900273526616cd"""
-import sys, os, hashlib, torch
-root = sys.argv[1] if len(sys.argv) > 1 else os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+"""Hash of the trained state of a full ViLT-B/32 engine after 12 hipGraph-replayed train_steps at configs[1]'s size, default
+settings: every group the step updates (_named_groups(), in that order: adapter_0, adapter_1, head for the dat engine).  Two builds
+with the same hash run the same arithmetic: at 80 steps the AdamW trajectory is chaotic enough that a last-bit change moves the
+round-length parity draws ("draws"), so a change meant to be arithmetic-neutral -- a kernel, or the host
+sequencing of an engine -- is checked with this before the 80-step tests are trusted.
+python tools/state_hash.py [repo root] [--engine dat | dat-fp8 | adapter | bias | norm]
+(the repo root is the tree whose feddat_amd is hashed, so one copy of this tool compares two trees)
+dat, round 6 HEAD (= round 5's arithmetic): cb900273526616cd; the other engines: DESIGN.md sections 13 and 14"""
+import argparse, sys, os, hashlib, torch
+ap = argparse.ArgumentParser()
+ap.add_argument("root", nargs="?", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+ap.add_argument("--engine", choices=("dat", "dat-fp8", "adapter", "bias", "norm"), default="dat")
+args = ap.parse_args()
+root = args.root
 sys.path.insert(0, root)
 from feddat_amd import engine, vilt_spec
 dev = torch.device("cuda", 0)
-params = vilt_spec.random_init(12, ["c0"], seed=0)
+mode = "dat" if args.engine.startswith("dat") else args.engine
+params = vilt_spec.random_init(12, ["c0"], seed=0, optimizer_mode=mode)
 batches = [vilt_spec.synthetic_batch(32, 384, 1234 + i, device=dev) for i in range(4)]
-e = engine.ViltDatEngine(params, ["c0"], dev, batch=32, res=384, layers=12)
-if hasattr(e, "top_q_cls"):
+size = dict(batch=32, res=384, layers=12)
+if mode == "dat":
+    e = engine.ViltDatEngine(params, ["c0"], dev, fp8=args.engine == "dat-fp8", **size)
     e.top_q_cls = False
+elif mode == "adapter":
+    from feddat_amd.adapter_engine import ViltAdapterEngine
+    e = ViltAdapterEngine(params, ["c0"], dev, **size)
+else:
+    from feddat_amd.vector_engine import ViltVectorEngine
+    e = ViltVectorEngine(params, ["c0"], dev, mode=mode, **size)
 e.begin_local_update("c0", steps_per_epoch=80)
 for i in range(12):
     e.train_step(batches[i % 4], use_graph=True)
 torch.cuda.synchronize()
 h = hashlib.sha256()
-for a in (0, 1):
-    h.update(e.ad[a].p.cpu().numpy().tobytes())
-h.update(e.head["c0"].p.cpu().numpy().tobytes())
-print(os.path.basename(root), h.hexdigest()[:16], float(e.ad[1].p.double().abs().sum()), float(e.loss_buf["p2"][0]))
+for _, grp in e._named_groups():
+    h.update(grp.p.cpu().numpy().tobytes())
+print(os.path.basename(root), args.engine, h.hexdigest()[:16], float(e.comm_flat().double().abs().sum()),
+      float(e._loss_tensor()[0]))
