@@ -83,7 +83,11 @@ class ViltAdapterEngine(ViltDatEngine):
         self._forward_dual()                       # embed, layers at R rows, token-0 top layer, pooler (B rows)
         logits = self._head_fwd(self.pooled[:B], "all", task)
         flag = self.ovf_flags[0:1]
-        L.bce_loss_fwd_bwd(logits, self.inp["target"], self.dlogits, self.loss_out, flag if self._dyn() else None)
+        if self.n_valid < B:      # a short batch: the loss of the n valid rows, zero gradient in the replica rows
+            L.bce_loss_fwd_bwd_rows(logits, self.inp["target"], self.dlogits, self.loss_out, self.n_valid,
+                                    flag if self._dyn() else None)
+        else:
+            L.bce_loss_fwd_bwd(logits, self.inp["target"], self.dlogits, self.loss_out, flag if self._dyn() else None)
         self._head_bwd(self.pooled[:B], "all", task, self.dpooled[:B])
         self._backward_dual()                      # layers L-1 .. 1, layer-0 weight gradients, one reduce (+ inf check)
         skip = dict(skip_if=(flag,)) if self._dyn() else {}

@@ -431,6 +431,64 @@ extern "C" int feddat_vilt_stage_inputs(const long* input_ids, const long* token
     FD_LAUNCH_RET();
 }
 
+// A short batch in the engine's static B-sample frame: sample j in [n, B) of every per-sample input of a step becomes a copy of
+// sample j mod n (finite activations and a non-empty key mask in the rows whose loss gradient is zero).  One launch:
+// blockIdx.z = buffer, blockIdx.y = tail sample, blockIdx.x strides over that sample's bytes.  A sample whose source and
+// destination are both 16-byte aligned moves as uint4 with a 4-byte tail; any other moves 4 bytes at a time (every
+// per-sample size is a multiple of 4: 16-bit patch rows of 3 P P elements, int64, fp32).
+#define FD_PAD_BUFS 6
+struct PadBatch {
+    char* base[FD_PAD_BUFS];
+    long bytes[FD_PAD_BUFS];       // per sample
+    int n;
+};
+__global__ __launch_bounds__(256) void pad_batch_kernel(PadBatch a) {
+    const long bytes = a.bytes[blockIdx.z];
+    const int j = a.n + blockIdx.y;
+    const char* src = a.base[blockIdx.z] + (long)(j % a.n) * bytes;
+    char* dst = a.base[blockIdx.z] + (long)j * bytes;
+    const long tid = (long)blockIdx.x * 256 + threadIdx.x, nthr = (long)gridDim.x * 256;
+    long done = 0;
+    if (((((uintptr_t)src) | ((uintptr_t)dst)) & 15) == 0) {
+        const long nv = bytes / 16;
+        const uint4* s4 = reinterpret_cast<const uint4*>(src);
+        uint4* d4 = reinterpret_cast<uint4*>(dst);
+        for (long i = tid; i < nv; i += nthr) d4[i] = s4[i];
+        done = nv * 16;
+    }
+    const uint32_t* s1 = reinterpret_cast<const uint32_t*>(src + done);
+    uint32_t* d1 = reinterpret_cast<uint32_t*>(dst + done);
+    const long nw = (bytes - done) / 4;
+    for (long i = tid; i < nw; i += nthr) d1[i] = s1[i];
+}
+
+extern "C" int feddat_vilt_pad_batch(void* patches_bf16, long* input_ids, long* token_type_ids, long* attention_mask,
+                                     long* patch_mask, float* target, int n, int B, int n_patches, int patch_elems, int Lt,
+                                     int n_labels, hipStream_t stream) {
+    FD_CHECK_ARG(patches_bf16 && input_ids && token_type_ids && attention_mask && patch_mask && target);
+    FD_CHECK_ARG(B > 0 && B <= 65535 && n >= 1 && n <= B && n_patches > 0 && patch_elems > 0 && patch_elems % 2 == 0 && Lt > 0 &&
+                 n_labels > 0);
+    FD_CHECK_ARG((((uintptr_t)patches_bf16 | (uintptr_t)input_ids | (uintptr_t)token_type_ids | (uintptr_t)attention_mask |
+                   (uintptr_t)patch_mask | (uintptr_t)target) & 3) == 0);
+    if (n == B) return FEDDAT_OK;
+    PadBatch a{};
+    void* base[FD_PAD_BUFS] = {patches_bf16, input_ids, token_type_ids, attention_mask, patch_mask, target};
+    const long bytes[FD_PAD_BUFS] = {(long)n_patches * patch_elems * 2, (long)Lt * 8, (long)Lt * 8, (long)Lt * 8,
+                                     (long)n_patches * 8, (long)n_labels * 4};
+    long most = 0;
+    for (int k = 0; k < FD_PAD_BUFS; ++k) {
+        a.base[k] = (char*)base[k];
+        a.bytes[k] = bytes[k];
+        most = max(most, bytes[k]);
+    }
+    a.n = n;
+    // grid.x is sized by the largest buffer (the patch matrix: 55 296 16-byte words per 384 x 384 sample, one word per thread and
+    // pass, capped at 64 blocks); for the five small buffers all blocks but the first find nothing to do, once per epoch
+    const unsigned gx = (unsigned)min((most / 16 + 255) / 256 + 1, 64L);
+    hipLaunchKernelGGL(pad_batch_kernel, dim3(gx, B - n, FD_PAD_BUFS), dim3(256), 0, stream, a);
+    FD_LAUNCH_RET();
+}
+
 extern "C" int feddat_cvt_f32_bf16(const float* in, void* out_bf16, long n, hipStream_t stream) {
     FD_CHECK_ARG(in && out_bf16 && n > 0);
     hipLaunchKernelGGL(cvt_kernel, dim3((unsigned)((n / 4 + 256) / 256)), dim3(256), 0, stream, in, (bf16*)out_bf16,

@@ -351,11 +351,10 @@ __global__ __launch_bounds__(256) void ht_ln_bwd_full_kernel(const float* __rest
 
 // DAT loss (task_trainer.py:299-301, 506-516) in ONE launch: wave w takes rows w, w + 16, ...; the batch sums run over
 // the row terms in LDS in the order of the two-kernel form (feddat_dat_loss_fwd_bwd), so both give the same bits.
-__global__ __launch_bounds__(1024) void dat_loss_single_kernel(const float* __restrict__ logits,
-                                                               const float* __restrict__ teacher,
-                                                               const float* __restrict__ target, int B, int C, float temp,
-                                                               float* __restrict__ dlogits, float* __restrict__ scalars,
-                                                               int* __restrict__ nonfinite) {
+__device__ __forceinline__ void dat_loss_single_body(const float* __restrict__ logits, const float* __restrict__ teacher,
+                                                     const float* __restrict__ target, int B, int C, float temp,
+                                                     float* __restrict__ dlogits, float* __restrict__ scalars,
+                                                     int* __restrict__ nonfinite) {
     extern __shared__ float terms[];       // [2 B]
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const float it = 1.0f / temp;
@@ -431,13 +430,38 @@ __global__ __launch_bounds__(1024) void dat_loss_single_kernel(const float* __re
     }
 }
 
+__global__ __launch_bounds__(1024) void dat_loss_single_kernel(const float* __restrict__ logits,
+                                                               const float* __restrict__ teacher,
+                                                               const float* __restrict__ target, int B, int C, float temp,
+                                                               float* __restrict__ dlogits, float* __restrict__ scalars,
+                                                               int* __restrict__ nonfinite) {
+    dat_loss_single_body(logits, teacher, target, B, C, temp, dlogits, scalars, nonfinite);
+}
+
+// A short batch in the static B-sample frame: rows [n, B) of dlogits become 0.0f (they hold the previous step's gradient
+// otherwise) and the loss runs on the n valid rows alone -- the same body with B = n, so rows [0, n) and the scalars carry the
+// bits of the full kernel on the n-row views and rows >= n of logits / teacher / target are never read.
+__device__ __forceinline__ void loss_zero_tail_rows(float* __restrict__ dlogits, int n, int B, int C) {
+    const size_t end = (size_t)B * C;
+    for (size_t i = (size_t)n * C + threadIdx.x; i < end; i += blockDim.x) dlogits[i] = 0.0f;
+}
+
+__global__ __launch_bounds__(1024) void dat_loss_rows_kernel(const float* __restrict__ logits,
+                                                             const float* __restrict__ teacher,
+                                                             const float* __restrict__ target, int n, int B, int C, float temp,
+                                                             float* __restrict__ dlogits, float* __restrict__ scalars,
+                                                             int* __restrict__ nonfinite) {
+    loss_zero_tail_rows(dlogits, n, B, C);
+    dat_loss_single_body(logits, teacher, target, n, C, temp, dlogits, scalars, nonfinite);
+}
+
 // Single-adapter step loss (optimizer_mode adapter; task_trainer.py:433-441): L = BCEWithLogits_mean(logits, target) * C and
 // dL/dlogits = (sigmoid(x) - t) / B in ONE launch.  Any C: lane j of a wave takes columns j, j + 64, ...; for C <= 128 a row's
 // terms are added in dat_loss_single_kernel's order and its batch sum is the same, so scalars[0] carries the same bits as
 // that kernel's BCE half.  Fixed-order reductions, no float atomics.
-__global__ __launch_bounds__(1024) void bce_loss_kernel(const float* __restrict__ logits, const float* __restrict__ target,
-                                                        int B, int C, float* __restrict__ dlogits,
-                                                        float* __restrict__ scalars, int* __restrict__ nonfinite) {
+__device__ __forceinline__ void bce_loss_body(const float* __restrict__ logits, const float* __restrict__ target, int B, int C,
+                                              float* __restrict__ dlogits, float* __restrict__ scalars,
+                                              int* __restrict__ nonfinite) {
     extern __shared__ float terms[];       // [B]
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const float inv_b = 1.0f / (float)B;
@@ -463,6 +487,19 @@ __global__ __launch_bounds__(1024) void bce_loss_kernel(const float* __restrict_
         scalars[0] = l_bce;
         if (nonfinite && fd_nonfinite(l_bce)) atomicOr(nonfinite, 1);
     }
+}
+
+__global__ __launch_bounds__(1024) void bce_loss_kernel(const float* __restrict__ logits, const float* __restrict__ target,
+                                                        int B, int C, float* __restrict__ dlogits,
+                                                        float* __restrict__ scalars, int* __restrict__ nonfinite) {
+    bce_loss_body(logits, target, B, C, dlogits, scalars, nonfinite);
+}
+
+__global__ __launch_bounds__(1024) void bce_loss_rows_kernel(const float* __restrict__ logits, const float* __restrict__ target,
+                                                             int n, int B, int C, float* __restrict__ dlogits,
+                                                             float* __restrict__ scalars, int* __restrict__ nonfinite) {
+    loss_zero_tail_rows(dlogits, n, B, C);
+    bce_loss_body(logits, target, n, C, dlogits, scalars, nonfinite);
 }
 
 __device__ __forceinline__ float ht_poly_lambda(int t, int warmup, int total) {     // = poly_lambda of loss_optim.hip
@@ -703,6 +740,15 @@ extern "C" int feddat_dat_loss_fwd_bwd_checked(const float* logits, const float*
     FD_LAUNCH_RET();
 }
 
+extern "C" int feddat_dat_loss_fwd_bwd_rows(const float* logits, const float* teacher, const float* target, int n, int B, int C,
+                                            float temp, float* dlogits, float* scalars, int* nonfinite, hipStream_t stream) {
+    FD_CHECK_ARG(logits && teacher && target && dlogits && scalars && n > 0 && n <= B && B <= 4096 && C > 0 && C <= 128 &&
+                 temp > 0.f);
+    hipLaunchKernelGGL(dat_loss_rows_kernel, dim3(1), dim3(1024), 2 * n * sizeof(float), stream, logits, teacher, target, n, B,
+                       C, temp, dlogits, scalars, nonfinite);
+    FD_LAUNCH_RET();
+}
+
 extern "C" int feddat_dat_step_finish(int* head_state, int* ad1_state, int* ad0_state, int* flags, float* scaler_f,
                                       int* scaler_i, float growth, float backoff, int growth_interval, hipStream_t stream) {
     FD_CHECK_ARG(head_state && ad1_state && ad0_state && flags && scaler_f && scaler_i && growth >= 1.0f && backoff > 0.f &&
@@ -752,6 +798,14 @@ extern "C" int feddat_bce_loss_fwd_bwd(const float* logits, const float* target,
     FD_CHECK_ARG(logits && target && dlogits && scalars && B > 0 && B <= 4096 && C > 0);
     hipLaunchKernelGGL(bce_loss_kernel, dim3(1), dim3(1024), B * sizeof(float), stream, logits, target, B, C, dlogits, scalars,
                        nonfinite);
+    FD_LAUNCH_RET();
+}
+
+extern "C" int feddat_bce_loss_fwd_bwd_rows(const float* logits, const float* target, int n, int B, int C, float* dlogits,
+                                            float* scalars, int* nonfinite, hipStream_t stream) {
+    FD_CHECK_ARG(logits && target && dlogits && scalars && n > 0 && n <= B && B <= 4096 && C > 0);
+    hipLaunchKernelGGL(bce_loss_rows_kernel, dim3(1), dim3(1024), n * sizeof(float), stream, logits, target, n, B, C, dlogits,
+                       scalars, nonfinite);
     FD_LAUNCH_RET();
 }
 

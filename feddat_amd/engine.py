@@ -195,6 +195,16 @@ class ViltDatEngine(ViltBackbone):
             if self.fp8_mx_dqkv:      # QKV^T: [768, 2304], per output channel
                 W["wqkvT8"], W["sqkvT"] = fp8_of(wqkv.t().contiguous())
 
+    # ------------------------------------------------------------------------------------------ inputs
+    def set_batch(self, batch: Dict[str, torch.Tensor]):
+        """ViltBackbone.set_batch; fp8=True takes full batches only: its gradient-row quantisers take row maxima and are not
+        verified on the all-zero gradient rows of a short batch."""
+        px = batch["pixel_values"]
+        if self.fp8 and px.dim() == 4 and 1 <= px.shape[0] < self.B:
+            raise L.FeddatHipError(f"fp8=True runs full batches only (got {px.shape[0]} of {self.B} samples): its gradient-row "
+                                   "quantisers are not verified on the all-zero rows of a short batch")
+        super().set_batch(batch)
+
     # ------------------------------------------------------------------------------------------ adapters
     def _alloc_pack(self, a, i):
         H, r = self.H, self.r
@@ -548,7 +558,11 @@ class ViltDatEngine(ViltBackbone):
         return [("adapter_0", self.ad[0]), ("adapter_1", self.ad[1]), ("head", self.head[self.task])]
 
     def _loss(self, logits, teacher, slot):
-        if self._dyn():      # + non-finite loss -> the sub-step's overflow flag (p1 = sub-step A, p2 = B)
+        if self.n_valid < self.B:      # a short batch: the loss of the n valid rows, zero gradient in the replica rows
+            flag = self.ovf_flags[1:2] if slot == "p1" else self.ovf_flags[0:1]
+            L.dat_loss_fwd_bwd_rows(logits, teacher, self.inp["target"], self.dlogits, self.loss_buf[slot], self.n_valid,
+                                    flag if self._dyn() else None)
+        elif self._dyn():      # + non-finite loss -> the sub-step's overflow flag (p1 = sub-step A, p2 = B)
             flag = self.ovf_flags[1:2] if slot == "p1" else self.ovf_flags[0:1]
             L.dat_loss_fwd_bwd_checked(logits, teacher, self.inp["target"], self.dlogits, self.loss_buf[slot], flag)
         elif self.fused_tail:
@@ -622,4 +636,4 @@ class ViltDatEngine(ViltBackbone):
             L.adapter_fwd(l0["h3"], h, self._single_segs(i, mode, R), R)
         self._pool(h, B)
         logits = self._head_fwd(self.pooled[:B], "all", task)
-        return self.pooled[:B].clone(), logits.clone()
+        return self.pooled[:self.n_valid].clone(), logits[:self.n_valid].clone()

@@ -151,6 +151,8 @@ _SIGS = {
     "feddat_dat_step_finish": [vp, vp, vp, vp, vp, vp, f32, f32, i32, vp],
     "feddat_bce_loss_fwd_bwd": [vp, vp, i32, i32, vp, vp, vp, vp],
     "feddat_single_step_finish": [C.POINTER(vp), i32, vp, vp, vp, f32, f32, i32, vp],
+    "feddat_dat_loss_fwd_bwd_rows": [vp, vp, vp, i32, i32, i32, f32, vp, vp, vp, vp],
+    "feddat_bce_loss_fwd_bwd_rows": [vp, vp, i32, i32, i32, vp, vp, vp, vp],
     "feddat_vector_grad_workspace_elems": [i32, i32],
     "feddat_colsum_partial": [vp, vp, i64, vp, i32, i32, vp, i64, vp],
     "feddat_ln_param_grad_partial": [vp, vp, i64, vp, i64, vp, i32, i32, vp, vp, i64, vp],
@@ -165,6 +167,7 @@ _SIGS = {
     "feddat_lm_loss_fwd_bwd_dyn": [vp, vp, i64, vp, vp, vp, i32, i32, f32, f32, f32, vp, vp, vp, i64, vp, vp],
     "feddat_axpby3": [vp, f32, vp, f32, vp, f32, vp, vp, i64, vp],
     "feddat_vilt_stage_inputs": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],
+    "feddat_vilt_pad_batch": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],
     "feddat_softmax_gather_rows": [vp, i64, i32, i32, vp, i64, i32, vp, vp],
     "feddat_topk_rows": [vp, i64, vp, i32, i32, i32, i32, vp, vp, vp],
     "feddat_gather_rows": [vp, vp, vp, vp, i32, i32, vp],
@@ -761,6 +764,28 @@ def bce_loss_fwd_bwd(logits, target, dlogits, scalars, nonfinite=None):
                                         _p(nonfinite), _stream()), "feddat_bce_loss_fwd_bwd")
 
 
+def dat_loss_fwd_bwd_rows(logits, teacher, target, dlogits, scalars, n, nonfinite=None, temp=3.0):
+    """The DAT loss of rows [0, n) of a B-row frame (n <= B = dlogits.shape[0]): dlogits[:n] and scalars[:3] as
+    dat_loss_fwd_bwd_checked gives on the [:n] views, dlogits[n:] = 0 (include/feddat_hip.h: feddat_dat_loss_fwd_bwd_rows)."""
+    _dev(logits, teacher, target, dlogits, scalars, nonfinite)
+    B, Cn = dlogits.shape
+    assert scalars.numel() >= 4 and (nonfinite is None or nonfinite.dtype == torch.int32)
+    assert logits.shape[0] >= n and teacher.shape[0] >= n and target.shape[0] >= n and logits.shape[1] == Cn
+    _chk(load().feddat_dat_loss_fwd_bwd_rows(_p(logits), _p(teacher), _p(target), int(n), B, Cn, temp, _p(dlogits), _p(scalars),
+                                             _p(nonfinite), _stream()), "feddat_dat_loss_fwd_bwd_rows")
+
+
+def bce_loss_fwd_bwd_rows(logits, target, dlogits, scalars, n, nonfinite=None):
+    """bce_loss_fwd_bwd of rows [0, n) of a B-row frame (n <= B = dlogits.shape[0]); dlogits[n:] = 0
+    (include/feddat_hip.h: feddat_bce_loss_fwd_bwd_rows)."""
+    _dev(logits, target, dlogits, scalars, nonfinite)
+    B, Cn = dlogits.shape
+    assert scalars.numel() >= 1 and (nonfinite is None or nonfinite.dtype == torch.int32)
+    assert logits.shape[0] >= n and target.shape[0] >= n and logits.shape[1] == Cn
+    _chk(load().feddat_bce_loss_fwd_bwd_rows(_p(logits), _p(target), int(n), B, Cn, _p(dlogits), _p(scalars), _p(nonfinite),
+                                             _stream()), "feddat_bce_loss_fwd_bwd_rows")
+
+
 # ---- gradients of per-column vectors (optimizer_mode bias / norm; include/feddat_hip.h, csrc/vector_grad.hip)
 def vector_grad_workspace_elems(rows: int, N: int) -> int:
     """Floats of one partial buffer for `rows` rows of N columns (slabs * N)."""
@@ -908,6 +933,26 @@ def vilt_stage_inputs(input_ids, token_type_ids, attention_mask, target, pixel_m
                                          _p(dst["input_ids"]), _p(dst["token_type_ids"]), _p(dst["attention_mask"]),
                                          _p(dst["target"]), _p(dst["patch_mask"]), B, Lt, n_labels, Hi, Wi, P, _stream()),
          "feddat_vilt_stage_inputs")
+
+
+def vilt_pad_batch_rc(patches, inp: dict, n: int, B: int) -> int:
+    """feddat_vilt_pad_batch on an engine's static inputs (patches: 16-bit [B * np, 3 P P]; inp: input_ids, token_type_ids,
+    attention_mask, patch_mask, target): samples [n, B) become copies of samples j mod n.  Returns the C return code."""
+    _dev(patches, *(inp[k] for k in ("input_ids", "token_type_ids", "attention_mask", "patch_mask", "target")))
+    assert patches.element_size() == 2 and patches.is_contiguous() and patches.shape[0] % B == 0
+    assert inp["target"].dtype == torch.float32 and all(
+        inp[k].dtype == torch.int64 and inp[k].is_contiguous() for k in ("input_ids", "token_type_ids", "attention_mask",
+                                                                         "patch_mask"))
+    n_patches = patches.shape[0] // B
+    assert inp["patch_mask"][:B].numel() == B * n_patches
+    return int(load().feddat_vilt_pad_batch(_p(patches), _p(inp["input_ids"]), _p(inp["token_type_ids"]),
+                                            _p(inp["attention_mask"]), _p(inp["patch_mask"]), _p(inp["target"]), int(n), int(B),
+                                            n_patches, patches.shape[1], inp["input_ids"].shape[1], inp["target"].shape[1],
+                                            _stream()))
+
+
+def vilt_pad_batch(patches, inp: dict, n: int, B: int):
+    _chk(vilt_pad_batch_rc(patches, inp, n, B), "feddat_vilt_pad_batch")
 
 
 def softmax_gather_rows(logits, rows, row_stride, V, ids, out):

@@ -62,6 +62,9 @@ class FlatGroup:
 class LocalUpdateEngine:
     # the adapter slot whose tensors the federation averages (comm_flat)
     COMM_ADAPTER = 1
+    # samples of the engine's static B-sample frame that the staged batch really holds (the ViLT engines' set_batch records
+    # it: a short last batch has n_valid < B); None: the engine takes full batches only
+    n_valid: Optional[int] = None
 
     # ------------------------------------------------------------------------------------------ loss scale
     def _init_loss_scale(self, operands: str, loss_scale: Optional[float], dynamic_loss_scale: Optional[bool],
@@ -209,12 +212,18 @@ class LocalUpdateEngine:
         (captured on first use).  Returns the engine's loss tensor (_loss_tensor)."""
         if batch is not None:
             self.set_batch(batch)
-        if not use_graph:
+        if not use_graph or self._short_batch():
+            # a short batch is never captured or replayed: its launch list differs (the loss kernels with a row count), and it
+            # comes once per epoch; the captured full-batch graph and its signature stay as they are
             self._step_kernels()
         else:
             self.ensure_captured()
             self.graph.replay()
         return self._loss_tensor()
+
+    def _short_batch(self) -> bool:
+        """The staged batch holds fewer samples than the engine's static frame."""
+        return self.n_valid is not None and self.n_valid < self.B
 
     @_bound
     def ensure_captured(self):
@@ -232,6 +241,11 @@ class LocalUpdateEngine:
         state = [t for g in groups for t in (g.p, g.m, g.v, g.state)] + [self.scaler_f, self.scaler_i, self.ovf_flags] + \
             self._extra_step_state()
         saved = [t.clone() for t in state]
+        # the graph is ALWAYS the full-batch launch list, whatever is staged (a loader whose only batch is short): the tail of
+        # the frame holds finite replicas then, and the staged row count comes back below
+        staged = self.n_valid
+        if staged is not None:
+            self.n_valid = self.B
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
@@ -251,6 +265,8 @@ class LocalUpdateEngine:
             if any(ad is g for g in groups):
                 self.repack_adapter(a)
         torch.cuda.synchronize()
+        if staged is not None:
+            self.n_valid = staged
         self.graph = graph
 
     # ------------------------------------------------------------------------------------------ state

@@ -327,6 +327,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--synthetic_label_alpha", type=float, default=0.0,
                    help="> 0: client k of the synthetic ViLT data draws its answers from its own Dirichlet(alpha) label prior "
                         "(SURVEY.md 8d config 3 uses 0.5: heterogeneous clients); 0 = uniform labels")
+    p.add_argument("--synthetic_last_batch", type=int, default=0,
+                   help="ViLT modes: samples in each client's LAST synthetic batch, 1 .. batch_size (a loader that does not drop "
+                        "its short last batch, like the reference's: vqa_dataset_crossvqa.py:509-515); 0 = every batch full")
     p.add_argument("--image_size", type=int, default=384)
     p.add_argument("--num_layers", type=int, default=12)
     p.add_argument("--albef_dropout", type=float, default=0.1,
@@ -365,6 +368,13 @@ def main(argv=None):
                                "row 13)")
     if mode != "dat" and "albef" in args.encoder_name:
         raise L.FeddatHipError("ALBEF supports only --optimizer_mode dat (adapter, bias and norm are ViLT modes here)")
+    if args.synthetic_last_batch:
+        if "albef" in args.encoder_name:
+            raise L.FeddatHipError("--synthetic_last_batch is a ViLT option: the ALBEF engine runs full batches only (the "
+                                   "reference's ALBEF train loader drops the last batch)")
+        if not 1 <= args.synthetic_last_batch <= args.batch_size:
+            raise L.FeddatHipError(f"--synthetic_last_batch must lie in 1 .. batch_size ({args.batch_size}), got "
+                                   f"{args.synthetic_last_batch}")
     logging.basicConfig(level=logging.INFO, format="%(asctime)s - %(levelname)s - %(message)s")
     log = logging.getLogger("feddat_amd")
     if args.mixed_precision is None:       # one default, the same as bench.py's and the engines' own
@@ -436,14 +446,16 @@ def main(argv=None):
         keep = set(mode_names(list(sd), mode)["personal"])
         return {n: v.clone() for n, v in sd.items() if n in keep}
     personal_params = {t: personal(model.state_dict()) for t in my_tasks}
-    def make_batch(seed, ti=0):
+    def make_batch(seed, ti=0, n=None):
         if albef:
             return albef_spec.synthetic_batch(args.batch_size, seed, image=args.image_size, vocab=dims.get("vocab", 30522),
                                               device=dev)
         prior = vilt_spec.client_label_prior(ti, alpha=args.synthetic_label_alpha) if args.synthetic_label_alpha > 0 else None
-        return vilt_spec.synthetic_batch(args.batch_size, args.image_size, seed, device=dev, label_prior=prior)
-    data = {t: [make_batch(args.seed + 1000 * ti + s, ti) for s in range(steps_of[t])] for ti, t in enumerate(tasks)
-            if t in my_tasks}
+        return vilt_spec.synthetic_batch(n or args.batch_size, args.image_size, seed, device=dev, label_prior=prior)
+    # --synthetic_last_batch N: the last batch of every client holds N samples (len(dataset) % batch_size != 0)
+    last = args.synthetic_last_batch or None
+    data = {t: [make_batch(args.seed + 1000 * ti + s, ti, last if s == steps_of[t] - 1 else None) for s in range(steps_of[t])]
+            for ti, t in enumerate(tasks) if t in my_tasks}
     server_flat = eng.comm_flat().clone()
     acc = torch.zeros_like(server_flat)
     # the exchange: one C-ABI collective per round (main.py:510 get_average_net -> feddat_fedavg_allreduce); the local

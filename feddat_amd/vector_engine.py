@@ -282,7 +282,11 @@ class ViltVectorEngine(ViltBackbone):
         self._forward_plain()
         logits = self._head_fwd(self.pooled[:B], "all", task)
         flag = self.ovf_flags[0:1]
-        L.bce_loss_fwd_bwd(logits, self.inp["target"], self.dlogits, self.loss_out, flag if self._dyn() else None)
+        if self.n_valid < B:      # a short batch: the loss of the n valid rows, zero gradient in the replica rows
+            L.bce_loss_fwd_bwd_rows(logits, self.inp["target"], self.dlogits, self.loss_out, self.n_valid,
+                                    flag if self._dyn() else None)
+        else:
+            L.bce_loss_fwd_bwd(logits, self.inp["target"], self.dlogits, self.loss_out, flag if self._dyn() else None)
         self._head_bwd(self.pooled[:B], "all", task, self.dpooled[:B])
         self._backward_plain()
         skip = dict(skip_if=(flag,)) if self._dyn() else {}
@@ -306,7 +310,7 @@ class ViltVectorEngine(ViltBackbone):
         self.set_batch(batch)
         self._forward_plain()
         logits = self._head_fwd(self.pooled[:self.B], "all", task)
-        return self.pooled[:self.B].clone(), logits.clone()
+        return self.pooled[:self.n_valid].clone(), logits[:self.n_valid].clone()
 
     def comm_flat(self) -> torch.Tensor:
         """The FedAvg payload: every trainable backbone vector back-to-back (the heads' own 'bias' / 'norm' keys are in the

@@ -176,6 +176,8 @@ class ViltBackbone(LocalUpdateEngine):
         self.dctx = b16(R2, H)
         self.dqkv = b16(R2, 3 * H)
         self.graph = None
+        # samples of the B-sample frame that the staged batch really holds (set_batch); B = a full batch
+        self.n_valid = batch
         self.ctx = L.Context(self.dev.index if self.dev.index is not None else torch.cuda.current_device())
         # True: the serial tail (token-0 LayerNorm + pooler, task head forward / backward, loss, optimizer bookkeeping) on the
         # fused kernels of csrc/head_tail.hip (20 launches); False: the round-3 sequence of 46 single-purpose launches (same
@@ -202,40 +204,55 @@ class ViltBackbone(LocalUpdateEngine):
     # ------------------------------------------------------------------------------------------ inputs
     @_bound
     def set_batch(self, batch: Dict[str, torch.Tensor]):
-        """Copy one batch (reference schema: HF ViLT encodings + target_scores) into the static input buffers."""
+        """Copy one batch (reference schema: HF ViLT encodings + target_scores) into the static input buffers.  A batch of
+        n < B samples (the last batch of a loader that does not drop it) is staged into samples [0, n) of the B-sample frame and
+        samples [n, B) become copies of samples j mod n; self.n_valid = n."""
         px = batch["pixel_values"]
-        if tuple(px.shape) != self._px_shape:
-            raise L.FeddatHipError(f"engine built for pixel_values {self._px_shape}, got {tuple(px.shape)}")
+        n = int(px.shape[0]) if px.dim() == 4 else 0
+        if px.dim() != 4 or tuple(px.shape[1:]) != self._px_shape[1:] or not 1 <= n <= self.B:
+            raise L.FeddatHipError(f"engine built for pixel_values {self._px_shape} (or fewer samples: a short last batch), "
+                                   f"got {tuple(px.shape)}")
         # the pixels are consumed right here, from the caller's tensor: patch extraction (im2col + bf16) is the only reader of
         # pixel_values, so it runs ahead of the captured step instead of a 57 MB device-to-device copy into a static buffer
         # followed by the same read inside the graph (stream-ordered with the replay that follows)
         if not px.is_cuda:
             px = px.to(self.dev, non_blocking=True)
-        L.im2col_patches(px.to(torch.float32).contiguous(), self.patches, self.B, 3, self.res[0], self.res[1], self.P)
+        L.im2col_patches(px.to(torch.float32).contiguous(), self.patches, n, 3, self.res[0], self.res[1], self.P)
+        self._stage_small_inputs(batch, n)
+        if n < self.B:
+            L.vilt_pad_batch(self.patches, self.inp, n, self.B)
+        self.n_valid = n
+
+    def _stage_small_inputs(self, batch, n: int):
+        """input_ids, token_type_ids, attention_mask, target_scores and pixel_mask of n samples -> samples [0, n) of self.inp."""
         ids, tts, am, tg, pm = (batch.get(k) for k in ("input_ids", "token_type_ids", "attention_mask", "target_scores",
                                                         "pixel_mask"))
 
         def dev_ok(t, dt, shape):
             return t is None or (t.is_cuda and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == shape)
-        B, Lt = self.B, self.Lt
-        if (ids is not None and tts is not None and dev_ok(ids, torch.int64, (B, Lt)) and dev_ok(tts, torch.int64, (B, Lt))
-                and dev_ok(am, torch.int64, (B, Lt)) and dev_ok(tg, torch.float32, (B, self.C))
-                and dev_ok(pm, torch.int64, (B, self.res[0], self.res[1]))):
+        Lt = self.Lt
+        if (ids is not None and tts is not None and dev_ok(ids, torch.int64, (n, Lt)) and dev_ok(tts, torch.int64, (n, Lt))
+                and dev_ok(am, torch.int64, (n, Lt)) and dev_ok(tg, torch.float32, (n, self.C))
+                and dev_ok(pm, torch.int64, (n, self.res[0], self.res[1]))):
             # the usual case (device-resident batch in the reference's dtypes): one launch for all five
-            L.vilt_stage_inputs(ids, tts, am, tg, pm, self.inp, B, Lt, self.C, self.res[0], self.res[1], self.P)
+            L.vilt_stage_inputs(ids, tts, am, tg, pm, self.inp, n, Lt, self.C, self.res[0], self.res[1], self.P)
             return
-        self.inp["input_ids"].copy_(batch["input_ids"], non_blocking=True)
-        self.inp["token_type_ids"].copy_(batch["token_type_ids"], non_blocking=True)
+        inp = {k: v[:n] for k, v in self.inp.items()}
+        for k in ("input_ids", "token_type_ids", "attention_mask", "target_scores", "pixel_mask"):
+            if batch.get(k) is not None and batch[k].shape[0] != n:
+                raise L.FeddatHipError(f"pixel_values has {n} samples but {k} has {batch[k].shape[0]}")
+        inp["input_ids"].copy_(batch["input_ids"], non_blocking=True)
+        inp["token_type_ids"].copy_(batch["token_type_ids"], non_blocking=True)
         if "target_scores" in batch:
-            self.inp["target"].copy_(batch["target_scores"], non_blocking=True)
+            inp["target"].copy_(batch["target_scores"], non_blocking=True)
         if batch.get("attention_mask") is not None:     # absent = all valid
-            self.inp["attention_mask"].copy_(batch["attention_mask"], non_blocking=True)
+            inp["attention_mask"].copy_(batch["attention_mask"], non_blocking=True)
         else:
-            self.inp["attention_mask"].fill_(1)
+            inp["attention_mask"].fill_(1)
         if batch.get("pixel_mask") is not None:
-            self.inp["patch_mask"].copy_(batch["pixel_mask"][:, ::self.P, ::self.P], non_blocking=True)
+            inp["patch_mask"].copy_(batch["pixel_mask"][:, ::self.P, ::self.P], non_blocking=True)
         else:
-            self.inp["patch_mask"].fill_(1)
+            inp["patch_mask"].fill_(1)
 
     # ------------------------------------------------------------------------------------------ forward
     def _embed(self):

@@ -512,6 +512,16 @@ int feddat_bce_loss_fwd_bwd(const float* logits, const float* target, int B, int
                             int* nonfinite, hipStream_t stream);
 int feddat_single_step_finish(int* const* states, int n, int* flag, float* scaler_f, int* scaler_i, float growth,
                               float backoff, int growth_interval, hipStream_t stream);
+/* A short last batch in a static B-row frame -- additions within ABI 8: the checked DAT loss and the
+ * BCE loss above with (n, B) in place of B, 1 <= n <= B <= 4096.  The loss and its means are those of rows [0, n) alone (BCE
+ * over n * C elements, KL batchmean over n): dlogits rows [0, n) and scalars[0..2] are bit-equal to
+ * feddat_dat_loss_fwd_bwd_checked / feddat_bce_loss_fwd_bwd called with B = n on the same pointers; dlogits rows [n, B) are
+ * written as 0.0f in the same launch (dlogits is [B, C]); rows >= n of logits / teacher / target are never read; *nonfinite
+ * (DEVICE int, may be NULL) follows the n valid rows only.  n == B is the full-batch result. */
+int feddat_dat_loss_fwd_bwd_rows(const float* logits, const float* teacher, const float* target, int n, int B, int C, float temp,
+                                 float* dlogits, float* scalars, int* nonfinite, hipStream_t stream);
+int feddat_bce_loss_fwd_bwd_rows(const float* logits, const float* target, int n, int B, int C, float* dlogits, float* scalars,
+                                 int* nonfinite, hipStream_t stream);
 
 /* Gradients of per-column vectors over a long row dimension (optimizer_mode bias / norm: a linear layer's bias, a LayerNorm's
  * gamma and beta over R = B * S rows) -- additions within ABI 8 (csrc/vector_grad.hip).  Two stages, both with a summation order
@@ -652,6 +662,14 @@ int feddat_vilt_stage_inputs(const long* input_ids, const long* token_type_ids, 
                              const long* pixel_mask, long* d_input_ids, long* d_token_type_ids, long* d_attention_mask,
                              float* d_target, long* d_patch_mask, int B, int Lt, int n_labels, int Hi, int Wi, int P,
                              hipStream_t stream);
+/* Addition within ABI 8: fills the tail of a ViLT engine's static input buffers when only samples [0, n) of the B-sample frame
+ * were staged.  One launch; for every j in [n, B), sample j of each buffer becomes a copy of sample j mod n: patches (16-bit
+ * [B * n_patches, patch_elems], patch_elems even), input_ids / token_type_ids / attention_mask (int64 [B, Lt]), patch_mask
+ * (int64 [B, n_patches]) and target (fp32 [B, n_labels], any n_labels).  Buffers 4-byte aligned (16-byte copies where a
+ * sample's source and destination allow, 4-byte copies otherwise).  Samples < n are not written; n == B launches nothing and
+ * returns FEDDAT_OK; n < 1 or n > B is FEDDAT_EINVAL and writes nothing. */
+int feddat_vilt_pad_batch(void* patches_bf16, long* input_ids, long* token_type_ids, long* attention_mask, long* patch_mask,
+                          float* target, int n, int B, int n_patches, int patch_elems, int Lt, int n_labels, hipStream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Input pipeline, image half: HF ViltImageProcessor as the reference calls it through
