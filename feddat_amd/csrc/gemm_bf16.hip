@@ -338,7 +338,7 @@ struct GemmArgsV2 {
     int bm;        // rows per M tile (<= 64 WM)
     int tiles_m;
     int nx, tm_per, tn_per;   // XCD grid (8 / nx) x nx, tiles per XCD along M / N (see v2_tile_coords)
-    int dbg;       // FEDDAT_GEMM_DEBUG ablation flags: 8 = skip epilogue; 32 / 64 = force WM 3 / 4; bits 8.. = block cap
+    int dbg;       // the route's flags (GemmRoute::dbg, 0 in production); read by the -DFEDDAT_ABLATE build only: 8 = skip epilogue
 };
 
 // Tile id -> tile.  Consecutive workgroups land on consecutive XCDs (8 private 4 MiB L2s), so tile_id & 7 is the XCD.
@@ -1497,134 +1497,125 @@ extern "C" int feddat_gemm_bf16_nt_skinny(const void* A, int lda, const void* B,
     FD_LAUNCH_RET();
 }
 
-namespace {
-}  // namespace
+#include "gemm_route.h"
 
-using V2Kernel = void (*)(GemmArgsV2);
-static const V2Kernel (*v2_kernel_table())[7] {
-    static const V2Kernel kernels[2][7] = {
-        {gemm_nt_v2_kernel<FEDDAT_EPI_BF16, 3>, gemm_nt_v2_kernel<FEDDAT_EPI_RESID_F32, 3>,
-         gemm_nt_v2_kernel<FEDDAT_EPI_GELU, 3>, gemm_nt_v2_kernel<FEDDAT_EPI_MUL_DGELU, 3>,
-         gemm_nt_v2_kernel<FEDDAT_EPI_F32, 3>, gemm_nt_v2_kernel<FEDDAT_EPI_GELU_G8, 3>,
-         gemm_nt_v2_kernel<FEDDAT_EPI_MUL_G8, 3>},
-        {gemm_nt_v2_kernel<FEDDAT_EPI_BF16, 4>, gemm_nt_v2_kernel<FEDDAT_EPI_RESID_F32, 4>,
-         gemm_nt_v2_kernel<FEDDAT_EPI_GELU, 4>, gemm_nt_v2_kernel<FEDDAT_EPI_MUL_DGELU, 4>,
-         gemm_nt_v2_kernel<FEDDAT_EPI_F32, 4>, gemm_nt_v2_kernel<FEDDAT_EPI_GELU_G8, 4>,
-         gemm_nt_v2_kernel<FEDDAT_EPI_MUL_G8, 4>}};
-    return kernels;
-}
+static_assert(fd_gemm_lds(FEDDAT_GEMM_V2, 192) == V2Cfg<3>::LDS && fd_gemm_lds(FEDDAT_GEMM_V2, 256) == V2Cfg<4>::LDS &&
+                  fd_gemm_lds(FEDDAT_GEMM_V3, 160) == V3Cfg<5>::LDS && fd_gemm_lds(FEDDAT_GEMM_V3, 192) == V3Cfg<6>::LDS &&
+                  fd_gemm_lds(FEDDAT_GEMM_V3, 224) == V3Cfg<7>::LDS && fd_gemm_lds(FEDDAT_GEMM_V3, 256) == V3Cfg<8>::LDS &&
+                  fd_gemm_lds(FEDDAT_GEMM_DUAL, 128) == 2 * V3Cfg<4>::STAGE && fd_gemm_lds(FEDDAT_GEMM_MID, 64) == MID_LDS &&
+                  fd_gemm_lds(FEDDAT_GEMM_V1, 128) == 4 * TILE_BYTES && V2_BN == 192 && BK == 64,
+              "gemm_route.h states the LDS plans and tile widths of the kernels above");
 
-static const V2Kernel (*v3_kernel_table())[5] {        // [0]: 192-row tiles (RT = 6), [1]: 256 (RT = 8), [2]: 160 (RT = 5), [3]: 224 (RT = 7)
-    static const V2Kernel kernels[4][5] = {
-        {gemm_nt_v3_kernel<FEDDAT_EPI_BF16, 6>, gemm_nt_v3_kernel<FEDDAT_EPI_RESID_F32, 6>, gemm_nt_v3_kernel<FEDDAT_EPI_GELU, 6>,
-         gemm_nt_v3_kernel<FEDDAT_EPI_MUL_DGELU, 6>, gemm_nt_v3_kernel<FEDDAT_EPI_F32, 6>},
-        {gemm_nt_v3_kernel<FEDDAT_EPI_BF16, 8>, gemm_nt_v3_kernel<FEDDAT_EPI_RESID_F32, 8>, gemm_nt_v3_kernel<FEDDAT_EPI_GELU, 8>,
-         gemm_nt_v3_kernel<FEDDAT_EPI_MUL_DGELU, 8>, gemm_nt_v3_kernel<FEDDAT_EPI_F32, 8>},
-        {gemm_nt_v3_kernel<FEDDAT_EPI_BF16, 5>, gemm_nt_v3_kernel<FEDDAT_EPI_RESID_F32, 5>, gemm_nt_v3_kernel<FEDDAT_EPI_GELU, 5>,
-         gemm_nt_v3_kernel<FEDDAT_EPI_MUL_DGELU, 5>, gemm_nt_v3_kernel<FEDDAT_EPI_F32, 5>},
-        {gemm_nt_v3_kernel<FEDDAT_EPI_BF16, 7>, gemm_nt_v3_kernel<FEDDAT_EPI_RESID_F32, 7>, gemm_nt_v3_kernel<FEDDAT_EPI_GELU, 7>,
-         gemm_nt_v3_kernel<FEDDAT_EPI_MUL_DGELU, 7>, gemm_nt_v3_kernel<FEDDAT_EPI_F32, 7>}};
-    return kernels;
+// The one kernel lookup: (family, tile rows, epilogue, operand kind, variant) -> persistent kernel, nullptr where none is built.
+//   16-bit operands: the two-group kernel (WM = rows / 64) and the dual form ("v4": gemm_nt_v3_kernel<E, 4, 0, true>) with every
+//   epilogue incl. the 8-bit codes, one wave per SIMD (RT = rows / 32) without the codes;
+//   fp8 (e4m3) operands, same two-group kernel: byte for byte the data movement of a bf16 product with K / 2 "elements" (128 fp8
+//   per 128-byte LDS row); only the MFMA -- ONE block-scaled v_mfma_scale_f32_16x16x128_f8f6f4 per output tile and k-tile, unit
+//   block scales, twice the bf16 rate -- and the dequantising epilogue differ.  GK_FP8_K32 (flag 256, tools/ A/B only; plain and
+//   GELU epilogue): the CDNA3-style K = 32 fp8 instruction it replaced, which issues at the bf16 rate.
+//   GK_DEFER_PROBE (-DFEDDAT_ABLATE, flag 512, tools/gemm_defer_probe.py): the deferred-epilogue timing probe (wrong results).
+using GemmKernel = void (*)(GemmArgsV2);
+enum { GK_PLAIN, GK_FP8_K32, GK_DEFER_PROBE };
+template <int E>
+static GemmKernel gemm_kernel_epi(int family, int rows, int kind, int variant) {
+    constexpr bool CODES = E == FEDDAT_EPI_GELU_G8 || E == FEDDAT_EPI_MUL_G8;
+    const bool r192 = rows == 192, r256 = rows == 256;
+    if (family == FEDDAT_GEMM_V2 && kind == FEDDAT_GEMM_FP8MX) {
+        if constexpr (E == FEDDAT_EPI_BF16)
+            return r192 ? gemm_nt_v2_kernel<E, 3, true, false, true> : r256 ? gemm_nt_v2_kernel<E, 4, true, false, true> : nullptr;
+    } else if (family == FEDDAT_GEMM_V2 && kind == FEDDAT_GEMM_FP8) {
+        if constexpr (E == FEDDAT_EPI_BF16 || E == FEDDAT_EPI_GELU)
+            if (variant == GK_FP8_K32)
+                return r192 ? gemm_nt_v2_kernel<E, 3, true, true> : r256 ? gemm_nt_v2_kernel<E, 4, true, true> : nullptr;
+        if constexpr (E == FEDDAT_EPI_MUL_DGELU || E == FEDDAT_EPI_RESID_F32) return r192 ? gemm_nt_v2_kernel<E, 3, true> : nullptr;
+        else return r192 ? gemm_nt_v2_kernel<E, 3, true> : r256 ? gemm_nt_v2_kernel<E, 4, true> : nullptr;
+    } else if constexpr (E <= FEDDAT_EPI_MUL_G8) {
+        if (kind != FEDDAT_GEMM_OP16) return nullptr;
+        if (family == FEDDAT_GEMM_DUAL && rows == 128) return gemm_nt_v3_kernel<E, 4, 0, true>;
+        if (family == FEDDAT_GEMM_V2) return r192 ? gemm_nt_v2_kernel<E, 3> : r256 ? gemm_nt_v2_kernel<E, 4> : nullptr;
+        if constexpr (!CODES) {
+#ifdef FEDDAT_ABLATE
+            if (family == FEDDAT_GEMM_V3 && variant == GK_DEFER_PROBE) return r192 ? gemm_nt_v3_kernel<E, 6, 1> : nullptr;
+#endif
+            if (family == FEDDAT_GEMM_V3)
+                return rows == 160 ? gemm_nt_v3_kernel<E, 5> : r192 ? gemm_nt_v3_kernel<E, 6> : rows == 224 ? gemm_nt_v3_kernel<E, 7>
+                       : r256      ? gemm_nt_v3_kernel<E, 8> : nullptr;
+        }
+    }
+    return nullptr;
 }
-// "v4": two independent 128-row workgroups per CU (gemm_nt_v3_kernel<E, 4, 0, true>), every epilogue incl. the 8-bit codes
-static const V2Kernel* v4_kernel_table() {
-    static const V2Kernel kernels[7] = {
-        gemm_nt_v3_kernel<FEDDAT_EPI_BF16, 4, 0, true>, gemm_nt_v3_kernel<FEDDAT_EPI_RESID_F32, 4, 0, true>,
-        gemm_nt_v3_kernel<FEDDAT_EPI_GELU, 4, 0, true>, gemm_nt_v3_kernel<FEDDAT_EPI_MUL_DGELU, 4, 0, true>,
-        gemm_nt_v3_kernel<FEDDAT_EPI_F32, 4, 0, true>, gemm_nt_v3_kernel<FEDDAT_EPI_GELU_G8, 4, 0, true>,
-        gemm_nt_v3_kernel<FEDDAT_EPI_MUL_G8, 4, 0, true>};
-    return kernels;
-}
-constexpr int V4_LDS = 2 * V3Cfg<4>::STAGE;      // 80 KiB: two workgroups fill the CU's 160 KiB exactly
-static int v3_lds(int which) {
-    return which == 1 ? V3Cfg<8>::LDS : which == 2 ? V3Cfg<5>::LDS : which == 3 ? V3Cfg<7>::LDS : V3Cfg<6>::LDS;
+static GemmKernel gemm_kernel(int family, int rows, int epi, int kind, int variant) {
+    static constexpr GemmKernel (*by_epi[])(int, int, int, int) = {
+        gemm_kernel_epi<0>, gemm_kernel_epi<1>, gemm_kernel_epi<2>, gemm_kernel_epi<3>, gemm_kernel_epi<4>,
+        gemm_kernel_epi<5>, gemm_kernel_epi<6>, gemm_kernel_epi<7>, gemm_kernel_epi<8>};
+    return epi < 0 || epi > FEDDAT_EPI_MUL_G8_F8 ? nullptr : by_epi[epi](family, rows, kind, variant);
 }
 
 // diagnostics: resident workgroups per CU the runtime grants the dual form (2 = the design point; 1 = it degenerates into a
 // one-wave-per-SIMD kernel with 128-row tiles)
 extern "C" int feddat_gemm_dual_blocks_per_cu(int* out) {
     FD_CHECK_ARG(out);
-    const V2Kernel k = v4_kernel_table()[FEDDAT_EPI_BF16];
-    if (fd_set_max_lds((const void*)k, V4_LDS) != FEDDAT_OK) return FEDDAT_ELAUNCH;
+    const GemmKernel k = gemm_kernel(FEDDAT_GEMM_DUAL, 128, FEDDAT_EPI_BF16, FEDDAT_GEMM_OP16, GK_PLAIN);
+    constexpr int lds = fd_gemm_lds(FEDDAT_GEMM_DUAL, 128);
+    if (fd_set_max_lds((const void*)k, lds) != FEDDAT_OK) return FEDDAT_ELAUNCH;
     int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)k, 256, V4_LDS) != hipSuccess) return FEDDAT_ELAUNCH;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)k, 256, lds) != hipSuccess) return FEDDAT_ELAUNCH;
     *out = n;
     return FEDDAT_OK;
 }
 
+// every kernel of the 16-bit entry point (the fp8 kernels set their attribute at their first launch)
 int fd_prepare_gemm_kernels() {
-    for (int w = 0; w < 4; ++w)
-        for (int e = 0; e < 5; ++e)
-            if (fd_set_max_lds((const void*)v3_kernel_table()[w][e], v3_lds(w)) != FEDDAT_OK) return FEDDAT_ELAUNCH;
-    for (int w = 0; w < 2; ++w)
-        for (int e = 0; e < 7; ++e)
-            if (fd_set_max_lds((const void*)v2_kernel_table()[w][e], w ? V2Cfg<4>::LDS : V2Cfg<3>::LDS) != FEDDAT_OK)
-                return FEDDAT_ELAUNCH;
-    for (int e = 0; e < 7; ++e)
-        if (fd_set_max_lds((const void*)v4_kernel_table()[e], V4_LDS) != FEDDAT_OK) return FEDDAT_ELAUNCH;
+    static const int tiles[][2] = {{FEDDAT_GEMM_V3, 192}, {FEDDAT_GEMM_V3, 256}, {FEDDAT_GEMM_V3, 160}, {FEDDAT_GEMM_V3, 224},
+                                   {FEDDAT_GEMM_V2, 192}, {FEDDAT_GEMM_V2, 256}, {FEDDAT_GEMM_DUAL, 128}};
+    for (const auto& t : tiles)
+        for (int e = 0; e <= FEDDAT_EPI_MUL_G8; ++e)
+            if (const GemmKernel k = gemm_kernel(t[0], t[1], e, FEDDAT_GEMM_OP16, GK_PLAIN))
+                if (fd_set_max_lds((const void*)k, fd_gemm_lds(t[0], t[1])) != FEDDAT_OK) return FEDDAT_ELAUNCH;
     if (fd_set_max_lds((const void*)gemm_nt_mid_kernel, MID_LDS) != FEDDAT_OK) return FEDDAT_ELAUNCH;
     return fd_set_max_lds((const void*)gemm_nt_kernel, 4 * TILE_BYTES);
 }
 
-// fp8 (e4m3) operands on the same persistent kernel: byte for byte the data movement of a bf16 product with K / 2
-// "elements" (128 fp8 per 128-byte LDS row); only the MFMA -- ONE block-scaled v_mfma_scale_f32_16x16x128_f8f6f4 per output
-// tile and k-tile, unit block scales, twice the bf16 rate (debug flag 256: the K = 32 fp8 instruction it replaced, which
-// issues at the bf16 rate) -- and the dequantising epilogue differ.
-// shared launch of the fp8 persistent kernel; EPI_RESID_F32 / EPI_F32 through feddat_gemm_fp8_nt_f32
-static int fp8_launch(GemmArgsV2& a2, int M, int N, int K, int epi, hipStream_t stream) {
-    GemmArgs& g = a2.g;
-    a2.dbg = FD_ABL(fd_debug_flags() & 8);       // -DFEDDAT_ABLATE build: 8 = skip the epilogue (k-loop timing)
+extern "C" int feddat_gemm_route(int M, int N, int K, int epi, int kind, int n_cu, int flags, feddat_gemm_route_t* out) {
+    FD_CHECK_ARG(out);
+    return fd_gemm_route(M, N, K, epi, kind, n_cu, flags, *out);
+}
+
+// the one launch: a missing kernel is an error
+template <class Args>
+static int gemm_launch(void (*kern)(Args), const GemmRoute& r, int grid, const Args& a, hipStream_t stream) {
+    FD_CHECK_ARG(kern);
+    if (fd_set_max_lds((const void*)kern, r.lds_bytes) != FEDDAT_OK) return FEDDAT_ELAUNCH;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(r.threads), r.lds_bytes, stream, a);
+    FD_LAUNCH_RET();
+}
+// ... of a persistent kernel: the route's tiling and flags go into GemmArgsV2 (dbg_abl: ablation-only bits, 0 in production)
+static int gemm_launch_persistent(const GemmArgs& g, const GemmRoute& r, int kind, int variant, int dbg_abl, int grid,
+                                  hipStream_t stream) {
+    GemmArgsV2 a2;
+    a2.g = g;
+    a2.bm = r.bm; a2.tiles_m = r.tiles_m; a2.nx = r.nx; a2.tm_per = r.tm_per; a2.tn_per = r.tn_per; a2.dbg = r.dbg | dbg_abl;
+    return gemm_launch(gemm_kernel(r.family, r.rows, g.epi, kind, variant), r, grid, a2, stream);
+}
+
+// the fp8 entry points: what their GemmArgs share (K and the leading dimensions in 2-byte units), then route and launch;
+// EPI_RESID_F32 / EPI_F32 through feddat_gemm_fp8_nt_f32
+static GemmArgs fp8_args(const void* A8, int lda, const float* a_scale, const void* B8, int ldb, const float* b_scale, int M, int N,
+                         int K, int epi, const float* bias) {
+    GemmArgs g{};
+    g.A = (const bf16*)A8; g.B = (const bf16*)B8; g.bias = bias; g.sa = a_scale; g.sw = b_scale;
+    g.M = M; g.N = N; g.K = K / 2; g.lda = lda / 2; g.ldb = ldb / 2; g.epi = epi;
+    return g;
+}
+static int fp8_launch(const GemmArgs& g, int K, hipStream_t stream) {
+    const int flags = fd_debug_flags();
     int n_cu = 0;
     if (fd_device_cus(&n_cu) != FEDDAT_OK) return FEDDAT_ELAUNCH;
-    const int tiles_n = N / V2_BN;
-    auto plan = [&](int BMx, GemmArgsV2& o) {
-        int nmt = (M + BMx - 1) / BMx;
-        o.nx = 1;
-        if ((size_t)N * K > (3u << 20) && tiles_n % 2 == 0 && nmt * tiles_n > n_cu) {
-            o.nx = 2;
-            nmt = (nmt + 3) & ~3;
-        }
-        const int bm = (M + nmt - 1) / nmt;
-        o.bm = bm;
-        o.tiles_m = o.nx == 1 ? (M + bm - 1) / bm : nmt;
-        o.tm_per = o.tiles_m / (8 / o.nx);
-        o.tn_per = tiles_n / o.nx;
-        return (o.tiles_m * tiles_n + n_cu - 1) / n_cu;
-    };
-    GemmArgsV2 a3 = a2, a4 = a2;
-    const int rounds3 = plan(192, a3), rounds4 = plan(256, a4);
-    // . gelu'(bf16 u) and the dequantising + residual epilogue stay on 192-row tiles (their 256-row instantiations spill)
-    const bool wm4 = rounds4 * 12 < rounds3 * 10 && epi != FEDDAT_EPI_MUL_DGELU && epi != FEDDAT_EPI_RESID_F32;
-    a2 = wm4 ? a4 : a3;
-    (void)g;
-    using KernelFn = void (*)(GemmArgsV2);
-    KernelFn kern = nullptr;
-#define FD_FP8_PICK(E) kern = wm4 ? gemm_nt_v2_kernel<E, 4, true> : gemm_nt_v2_kernel<E, 3, true>
-    switch (epi) {
-        case FEDDAT_EPI_MUL_DGELU: kern = gemm_nt_v2_kernel<FEDDAT_EPI_MUL_DGELU, 3, true>; break;
-        case FEDDAT_EPI_MUL_G8: FD_FP8_PICK(FEDDAT_EPI_MUL_G8); break;
-        case FEDDAT_EPI_GELU_G8: FD_FP8_PICK(FEDDAT_EPI_GELU_G8); break;
-        case FEDDAT_EPI_MUL_G8_F8: FD_FP8_PICK(FEDDAT_EPI_MUL_G8_F8); break;
-        case FEDDAT_EPI_GELU_G8_F8: FD_FP8_PICK(FEDDAT_EPI_GELU_G8_F8); break;
-        case FEDDAT_EPI_RESID_F32: kern = gemm_nt_v2_kernel<FEDDAT_EPI_RESID_F32, 3, true>; break;
-        case FEDDAT_EPI_F32: FD_FP8_PICK(FEDDAT_EPI_F32); break;
-        case FEDDAT_EPI_BF16:
-            if (g.amx) kern = wm4 ? gemm_nt_v2_kernel<FEDDAT_EPI_BF16, 4, true, false, true> : gemm_nt_v2_kernel<FEDDAT_EPI_BF16, 3, true, false, true>;
-            else if (fd_debug_flags() & 256) kern = wm4 ? gemm_nt_v2_kernel<FEDDAT_EPI_BF16, 4, true, true> : gemm_nt_v2_kernel<FEDDAT_EPI_BF16, 3, true, true>;
-            else FD_FP8_PICK(FEDDAT_EPI_BF16);
-            break;
-        case FEDDAT_EPI_GELU:      // debug flag 256, tools/ A/B only: the CDNA3-style K = 32 fp8 instruction (bf16 issue rate)
-            if (fd_debug_flags() & 256) kern = wm4 ? gemm_nt_v2_kernel<FEDDAT_EPI_GELU, 4, true, true> : gemm_nt_v2_kernel<FEDDAT_EPI_GELU, 3, true, true>;
-            else FD_FP8_PICK(FEDDAT_EPI_GELU);
-            break;
-        default: return FEDDAT_EINVAL;
-    }
-#undef FD_FP8_PICK
-    const int lds_bytes = (wm4 ? V2Cfg<4>::LDS : V2Cfg<3>::LDS) + (g.amx ? 2 * 256 * (wm4 ? 4 : 3) : 0);   // MXA: + the scale stages
-    if (fd_set_max_lds((const void*)kern, lds_bytes) != FEDDAT_OK) return FEDDAT_ELAUNCH;
-    const int total = a2.tiles_m * tiles_n;
-    hipLaunchKernelGGL(kern, dim3(total < n_cu ? total : n_cu), dim3(512), lds_bytes, stream, a2);
-    FD_LAUNCH_RET();
+    const int kind = g.amx ? FEDDAT_GEMM_FP8MX : FEDDAT_GEMM_FP8;
+    GemmRoute r;
+    FD_CHECK_ARG(fd_gemm_route(g.M, g.N, K, g.epi, kind, n_cu, flags, r) == FEDDAT_OK);
+    // -DFEDDAT_ABLATE build: 8 = skip the epilogue (k-loop timing)
+    return gemm_launch_persistent(g, r, kind, (flags & 256) ? GK_FP8_K32 : GK_PLAIN, FD_ABL(flags & 8), r.grid, stream);
 }
 
 extern "C" int feddat_gemm_fp8mx_nt(const void* A8, int lda, const uint8_t* a_mx, int ld_mx, const void* B8, int ldb,
@@ -1633,13 +1624,9 @@ extern "C" int feddat_gemm_fp8mx_nt(const void* A8, int lda, const uint8_t* a_mx
     FD_CHECK_ARG(A8 && a_mx && B8 && b_scale && out_bf16 && M >= 1024 && N > 0 && N % V2_BN == 0 && K > 0 && K % 128 == 0);
     FD_CHECK_ARG(lda % 16 == 0 && ldb % 16 == 0 && lda >= K && ldb >= K && ((uintptr_t)out_bf16 & 15) == 0 && ldo16 % 8 == 0);
     FD_CHECK_ARG(ld_mx % 4 == 0 && ld_mx >= K / 32 && ((uintptr_t)a_mx & 3) == 0);
-    GemmArgsV2 a2;
-    GemmArgs& g = a2.g;
-    g = GemmArgs{};
-    g.A = (const bf16*)A8; g.B = (const bf16*)B8; g.bias = bias; g.sa = nullptr; g.sw = b_scale; g.amx = a_mx; g.ld_mx = ld_mx;
-    g.out_bf16 = (bf16*)out_bf16;
-    g.M = M; g.N = N; g.K = K / 2; g.lda = lda / 2; g.ldb = ldb / 2; g.ldo16 = ldo16; g.epi = FEDDAT_EPI_BF16;
-    return fp8_launch(a2, M, N, K, FEDDAT_EPI_BF16, stream);
+    GemmArgs g = fp8_args(A8, lda, nullptr, B8, ldb, b_scale, M, N, K, FEDDAT_EPI_BF16, bias);
+    g.amx = a_mx; g.ld_mx = ld_mx; g.out_bf16 = (bf16*)out_bf16; g.ldo16 = ldo16;
+    return fp8_launch(g, K, stream);
 }
 
 extern "C" int feddat_gemm_fp8_nt(const void* A8, int lda, const float* a_scale, const void* B8, int ldb,
@@ -1657,14 +1644,10 @@ extern "C" int feddat_gemm_fp8_nt(const void* A8, int lda, const float* a_scale,
     FD_CHECK_ARG(lda % 16 == 0 && ldb % 16 == 0 && lda >= K && ldb >= K && ((uintptr_t)out_bf16 & 15) == 0);
     FD_CHECK_ARG(f8out ? (ldo16 % 16 == 0 && ldo16 >= N) : ldo16 % 8 == 0);
     FD_CHECK_ARG(!out2_bf16 || (ldo2 % 8 == 0 && ((uintptr_t)out2_bf16 & 15) == 0));
-    GemmArgsV2 a2;
-    GemmArgs& g = a2.g;
-    g = GemmArgs{};
-    g.A = (const bf16*)A8; g.B = (const bf16*)B8; g.bias = bias; g.sa = a_scale; g.sw = b_scale;
+    GemmArgs g = fp8_args(A8, lda, a_scale, B8, ldb, b_scale, M, N, K, epi, bias);
     g.aux = (const bf16*)aux; g.ldaux = ldaux;
-    g.out_bf16 = (bf16*)out_bf16; g.out2_bf16 = (bf16*)out2_bf16;
-    g.M = M; g.N = N; g.K = K / 2; g.lda = lda / 2; g.ldb = ldb / 2; g.ldo16 = ldo16; g.ldo2 = ldo2; g.epi = epi;
-    return fp8_launch(a2, M, N, K, epi, stream);
+    g.out_bf16 = (bf16*)out_bf16; g.out2_bf16 = (bf16*)out2_bf16; g.ldo16 = ldo16; g.ldo2 = ldo2;
+    return fp8_launch(g, K, stream);
 }
 
 extern "C" int feddat_gemm_fp8_nt_f32(const void* A8, int lda, const float* a_scale, const void* B8, int ldb,
@@ -1673,14 +1656,9 @@ extern "C" int feddat_gemm_fp8_nt_f32(const void* A8, int lda, const float* a_sc
     FD_CHECK_ARG(A8 && B8 && a_scale && b_scale && out_f32 && M >= 1024 && N > 0 && N % V2_BN == 0 && K > 0 && K % 128 == 0);
     FD_CHECK_ARG(lda % 16 == 0 && ldb % 16 == 0 && lda >= K && ldb >= K && ldo32 % 4 == 0 && ldo32 >= N);
     FD_CHECK_ARG(!resid || (ldr % 4 == 0 && ldr >= N && (size_t)M * ldr * 4 < (1ull << 32)));
-    GemmArgsV2 a2;
-    GemmArgs& g = a2.g;
-    g = GemmArgs{};
-    g.A = (const bf16*)A8; g.B = (const bf16*)B8; g.bias = bias; g.sa = a_scale; g.sw = b_scale;
+    GemmArgs g = fp8_args(A8, lda, a_scale, B8, ldb, b_scale, M, N, K, resid ? FEDDAT_EPI_RESID_F32 : FEDDAT_EPI_F32, bias);
     g.resid = resid; g.ldr = ldr; g.out_f32 = out_f32; g.ldo32 = ldo32;
-    const int epi = resid ? FEDDAT_EPI_RESID_F32 : FEDDAT_EPI_F32;
-    g.M = M; g.N = N; g.K = K / 2; g.lda = lda / 2; g.ldb = ldb / 2; g.epi = epi;
-    return fp8_launch(a2, M, N, K, epi, stream);
+    return fp8_launch(g, K, stream);
 }
 
 extern "C" int feddat_gemm_bf16_nt(const void* A, int lda, const void* B, int ldb, int M, int N, int K, int epi,
@@ -1688,22 +1666,13 @@ extern "C" int feddat_gemm_bf16_nt(const void* A, int lda, const void* B, int ld
                                    float* out_f32, int ldo32, void* out_bf16, int ldo16, void* out2_bf16, int ldo2,
                                    hipStream_t stream) {
     FD_CHECK_ARG(A && B && M > 0 && N > 0 && K > 0);
-    bool use_v2 = (N % V2_BN == 0) && (K % BK == 0) && (M >= 1024);
-    // Medium M (ALBEF's stacked text streams: 2 x 800 rows): the persistent kernels would put 1600 x 768 on 9 x 4 = 36 tiles, i.e.
-    // 36 of the 256 CUs; the small-tile kernel fills the chip with 64 x 64 tiles (same k order: bit-identical results).  Taken
-    // when a launch has fewer 192-row tiles than 0.6 x the CUs; not for the gelu' code epilogues (persistent kernels only);
-    // debug flag 1 (everything on the two-group persistent kernel) keeps the old routing (A/B: tools/albef_stack_ab.py).
-    bool small_grid = false;
-    if (use_v2 && M < 4096 && epi != FEDDAT_EPI_GELU_G8 && epi != FEDDAT_EPI_MUL_G8 && !(fd_debug_flags() & 1)) {
-        int n_cu = 0;
-        if (fd_device_cus(&n_cu) != FEDDAT_OK) return FEDDAT_ELAUNCH;
-        // (debug flag 128 = "no small-tile kernel": such launches stay on the persistent kernel instead of falling through to the
-        //  128 x 128 kernel, which needs N % 128 == 0 -- N = 192 x odd would silently lose its tail columns there)
-        small_grid = ((M + 191) / 192) * (N / V2_BN) * 10 < n_cu * 6 && !(fd_debug_flags() & 128);
-        if (small_grid) use_v2 = false;
-    }
-    FD_CHECK_ARG((N % BN == 0 || use_v2 || ((M < 1024 || small_grid) && N % 64 == 0)) && K % BK == 0);
     FD_CHECK_ARG(lda % 8 == 0 && ldb % 8 == 0 && lda >= K && ldb >= K);
+    const int flags = fd_debug_flags();            // tools/ only (feddat_set_debug_flags); 0 in production
+    int n_cu = 0;
+    if (fd_device_cus(&n_cu) != FEDDAT_OK) return FEDDAT_ELAUNCH;
+    GemmRoute r;
+    FD_CHECK_ARG(fd_gemm_route(M, N, K, epi, FEDDAT_GEMM_OP16, n_cu, flags, r) == FEDDAT_OK);
+    const bool use_v2 = r.family >= FEDDAT_GEMM_V2;      // a persistent kernel
     switch (epi) {
         case FEDDAT_EPI_BF16: FD_CHECK_ARG(out_bf16 && ldo16 % 4 == 0); break;
         case FEDDAT_EPI_RESID_F32:
@@ -1723,10 +1692,8 @@ extern "C" int feddat_gemm_bf16_nt(const void* A, int lda, const void* B, int ld
             break;
         default: return FEDDAT_EINVAL;
     }
-    const bool g8 = epi == FEDDAT_EPI_GELU_G8 || epi == FEDDAT_EPI_MUL_G8;
     if (use_v2) {      // 16-byte bf16 stores / aux loads of the persistent kernel's epilogue
-        if (epi == FEDDAT_EPI_BF16 || epi == FEDDAT_EPI_GELU || epi == FEDDAT_EPI_MUL_DGELU || g8)
-            FD_CHECK_ARG(ldo16 % 8 == 0 && ((uintptr_t)out_bf16 & 15) == 0);
+        if (epi != FEDDAT_EPI_RESID_F32 && epi != FEDDAT_EPI_F32) FD_CHECK_ARG(ldo16 % 8 == 0 && ((uintptr_t)out_bf16 & 15) == 0);
         if (epi == FEDDAT_EPI_GELU && out2_bf16) FD_CHECK_ARG(ldo2 % 8 == 0 && ((uintptr_t)out2_bf16 & 15) == 0);
         if (epi == FEDDAT_EPI_MUL_DGELU) FD_CHECK_ARG(ldaux % 8 == 0 && ((uintptr_t)aux & 15) == 0);
     }
@@ -1735,122 +1702,19 @@ extern "C" int feddat_gemm_bf16_nt(const void* A, int lda, const void* B, int ld
     g.out_f32 = out_f32; g.out_bf16 = (bf16*)out_bf16; g.out2_bf16 = (bf16*)out2_bf16;
     g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldb = ldb; g.ldr = ldr; g.ldaux = ldaux;
     g.ldo32 = ldo32; g.ldo16 = ldo16; g.ldo2 = ldo2; g.epi = epi;
-    g.nostore = FD_ABL(((fd_debug_flags() & 16) ? 1 : 0) | ((fd_debug_flags() & 4) ? 2 : 0));   // 4: ablate the GELU math
-    if (use_v2) {
-        GemmArgsV2 a2;
-        a2.g = g;
-        int dbg = fd_debug_flags();            // tools/ ablations only (feddat_set_debug_flags); 0 in production
-        a2.dbg = dbg;
-        int n_cu = 0;
-        if (fd_device_cus(&n_cu) != FEDDAT_OK) return FEDDAT_ELAUNCH;
-        // tools/overlap_probe.py: bits 28..31 of the debug flags cap the persistent grid at 16 x value workgroups, so that a
-        // launch on a side stream leaves compute units to the kernels of the main stream
-        if (const int cap16 = (dbg >> 28) & 0xf) n_cu = n_cu < cap16 * 16 ? n_cu : cap16 * 16;
-        const int tiles_n = N / V2_BN;
-        // balanced M tiles of <= BM rows; XCD-aware tile order: split the XCDs over N as well when B (N x K bf16) would
-        // not stay in a 4 MiB L2 and the launch takes more than one round of tiles
-        auto plan = [&](int BMx, GemmArgsV2& o) {
-            int nmt = (M + BMx - 1) / BMx;
-            o.nx = 1;
-            if ((size_t)N * K * 2 > (3u << 20) && tiles_n % 2 == 0 && nmt * tiles_n > n_cu) {
-                o.nx = 2;
-                nmt = (nmt + 3) & ~3;                      // 4 M groups of equal size
-            }
-            const int bm = (M + nmt - 1) / nmt;
-            o.bm = bm;
-            o.tiles_m = o.nx == 1 ? (M + bm - 1) / bm : nmt;
-            o.tm_per = o.tiles_m / (8 / o.nx);
-            o.tn_per = tiles_n / o.nx;
-            return (o.tiles_m * tiles_n + n_cu - 1) / n_cu;     // rounds of the persistent grid
-        };
-        // The DUAL form (selection flags 1 | 2 together: every persistent launch; 1 | 2 | 64: only launches of at least two full
-        // rounds of the doubled grid, e.g. N = 3072 at M = 11 840: 96 x 16 tiles = 3.0 rounds of 512): two independent 128-row
-        // workgroups per CU.  Measured, not the default: profiles/r06_gemm_dual_ab.txt, DESIGN.md section 7e.
-        if ((dbg & 3) == 3 && K / BK >= 3) {      // (its self-contained tiles need a first, a penultimate and a last k-tile)
-            GemmArgsV2 a1 = a2;
-            const int cu1 = n_cu;
-            n_cu *= 2;
-            plan(128, a1);
-            n_cu = cu1;
-            const int total1 = a1.tiles_m * tiles_n;
-            if (!(dbg & 64) || total1 >= 4 * n_cu) {
-                const V2Kernel k4 = v4_kernel_table()[epi];
-                if (fd_set_max_lds((const void*)k4, V4_LDS) != FEDDAT_OK) return FEDDAT_ELAUNCH;
-                hipLaunchKernelGGL(k4, dim3(total1 < 2 * n_cu ? total1 : 2 * n_cu), dim3(256), V4_LDS, stream, a1);
-                FD_LAUNCH_RET();
-            }
-        }
-        if ((dbg & 3) == 3) {       // not taken: the production routing below
-            dbg &= ~3;
-            a2.dbg = dbg;
-        }
-        GemmArgsV2 a3 = a2, a4 = a2, a5 = a2, a7 = a2;
-        const int rounds3 = plan(192, a3), rounds4 = plan(256, a4), rounds5 = plan(160, a5), rounds7 = plan(224, a7);
-        // a 256-row tile costs about 1.2x a 192-row tile (48 vs 36 MFMAs per k-tile and wave, L phase 20 vs 18 reads)
-        bool wm4 = rounds4 * 12 < rounds3 * 10;
-        if (epi == FEDDAT_EPI_MUL_DGELU) wm4 = false;      // its 256-row instantiation spills (180 B of scratch per lane and tile)
-        if (dbg & 32) wm4 = false;
-        if (dbg & 64) wm4 = true;
-        a2 = wm4 ? a4 : a3;
-        // v3 (one wave per SIMD) has the faster k-loop (1.1-1.28 PF/s against 0.96-1.15) but only four waves to run an
-        // epilogue: it takes every launch except the two heavy epilogues (GELU with two outputs; . gelu'(aux) with its cold
-        // aux operand) -- in isolation v3 is level or ahead on those too (84 against 98 us for . gelu'), in the step, with
-        // nothing cache-warm, it is behind (86 / 89 us against 82 / 81: tools/step_breakdown.py --detail); debug flag 1
-        // keeps everything on v2, flag 2 forces v3
-        const bool v3_pick = epi != FEDDAT_EPI_GELU && epi != FEDDAT_EPI_MUL_DGELU && !g8;
-        if (g8 && (dbg & (2 | 512))) return FEDDAT_EINVAL;      // the code epilogues exist on the two-group (and the dual) kernel only
+    g.nostore = FD_ABL(((flags & 16) ? 1 : 0) | ((flags & 4) ? 2 : 0));   // 16: no stores; 4: ablate the GELU math
+    if (!use_v2) return gemm_launch(r.family == FEDDAT_GEMM_MID ? gemm_nt_mid_kernel : gemm_nt_kernel, r, r.grid, g, stream);
+    int variant = GK_PLAIN, grid = r.grid;
 #ifdef FEDDAT_ABLATE
-        if (dbg & 512) {        // tools/gemm_defer_probe.py: the deferred-epilogue timing probe (RT = 6; wrong results)
-            static const V2Kernel fk[5] = {gemm_nt_v3_kernel<FEDDAT_EPI_BF16, 6, 1>, gemm_nt_v3_kernel<FEDDAT_EPI_RESID_F32, 6, 1>,
-                                           gemm_nt_v3_kernel<FEDDAT_EPI_GELU, 6, 1>, gemm_nt_v3_kernel<FEDDAT_EPI_MUL_DGELU, 6, 1>,
-                                           gemm_nt_v3_kernel<FEDDAT_EPI_F32, 6, 1>};
-            a2 = a3;
-            if (fd_set_max_lds((const void*)fk[epi], V3Cfg<6>::LDS) != FEDDAT_OK) return FEDDAT_ELAUNCH;
-            const int total3 = a2.tiles_m * (N / V2_BN);
-            hipLaunchKernelGGL(fk[epi], dim3(total3 < n_cu ? total3 : n_cu), dim3(256), V3Cfg<6>::LDS, stream, a2);
-            FD_LAUNCH_RET();
-        }
+    if ((r.dbg & 512) && r.family != FEDDAT_GEMM_DUAL) {      // the deferred-epilogue probe: one wave per SIMD, 192-row tiles
+        const int dbg = r.dbg;
+        FD_CHECK_ARG(fd_gemm_route(M, N, K, epi, FEDDAT_GEMM_OP16, n_cu, (dbg & ~(1 | 64)) | 2 | 32 | 128, r) == FEDDAT_OK);
+        r.dbg = dbg;
+        variant = GK_DEFER_PROBE;
+        grid = r.grid;
+    }
+    const int cap = (r.dbg >> 8) & 0xfff;      // cap the number of persistent blocks of the two-group kernel
+    if (r.family == FEDDAT_GEMM_V2 && cap > 0 && cap < grid) grid = cap;
 #endif
-        if (((dbg & 2) || v3_pick) && !(dbg & 1)) {
-            const bool rt8 = (dbg & 64) ? true : (dbg & 32) ? false : wm4;
-            // 160-row tiles (RT = 5, ~0.87 of a 192-row tile's time) where they fill the rounds better: 18 464 rows x N = 768
-            // (ALBEF's ViT) = 388 tiles of 192 rows = 1.52 rounds of the 256 CUs, paid as 2; 464 tiles of 160 rows = 1.81 rounds,
-            // paid as 2 x 0.87.  configs[1]'s 11 840 rows (64 x 185) keep their exact rounds of 192-row tiles.
-            // 224-row tiles (RT = 7, ~1.1 of a 192-row tile's time) likewise: 18 464 rows x N = 2304 = 4 rounds of either 256- or
-            // 224-row tiles
-            const int cost68 = rt8 ? rounds4 * 120 : rounds3 * 100;
-            const bool odd_ok = !(dbg & (32 | 64 | (1 << 27)));
-            const bool rt5 = odd_ok && rounds5 * 87 < cost68 && rounds5 * 87 <= rounds7 * 110;
-            const bool rt7 = odd_ok && !rt5 && rounds7 * 110 < cost68;
-            const int which = rt5 ? 2 : rt7 ? 3 : rt8 ? 1 : 0;
-            const V2Kernel k3 = v3_kernel_table()[which][epi];
-            a2 = rt5 ? a5 : rt7 ? a7 : rt8 ? a4 : a3;
-            const int lds3 = v3_lds(which);
-            if (fd_set_max_lds((const void*)k3, lds3) != FEDDAT_OK) return FEDDAT_ELAUNCH;
-            const int total3 = a2.tiles_m * (N / V2_BN);
-            hipLaunchKernelGGL(k3, dim3(total3 < n_cu ? total3 : n_cu), dim3(256), lds3, stream, a2);
-            FD_LAUNCH_RET();
-        }
-        const V2Kernel kern = v2_kernel_table()[wm4 ? 1 : 0][epi];
-        const int lds_bytes = wm4 ? V2Cfg<4>::LDS : V2Cfg<3>::LDS;
-        if (fd_set_max_lds((const void*)kern, lds_bytes) != FEDDAT_OK) return FEDDAT_ELAUNCH;
-        const int total = a2.tiles_m * (N / V2_BN);
-        int grid = total < n_cu ? total : n_cu;
-        if (FD_ABL((dbg >> 8) & 0xfff) > 0 && FD_ABL((dbg >> 8) & 0xfff) < grid) grid = (dbg >> 8) & 0xfff;      // ablation: cap the number of persistent blocks
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds_bytes, stream, a2);
-        FD_LAUNCH_RET();
-    }
-    // few rows and too few 128 x 128 tiles to fill the chip: the latency-oriented small-tile kernel
-    const bool v1_ok = N % BN == 0;
-    if ((M < 1024 || small_grid) && N % 64 == 0 && (!v1_ok || ((M + BM - 1) / BM) * (N / BN) < 150) && !(fd_debug_flags() & 128)) {
-        const int tm = (M + 63) / 64;
-        if (fd_set_max_lds((const void*)gemm_nt_mid_kernel, MID_LDS) != FEDDAT_OK) return FEDDAT_ELAUNCH;
-        hipLaunchKernelGGL(gemm_nt_mid_kernel, dim3(tm * (N / 64)), dim3(256), MID_LDS, stream, g);
-        FD_LAUNCH_RET();
-    }
-    FD_CHECK_ARG(v1_ok);      // the 128 x 128 kernel has no column tail
-    const int tiles = ((M + BM - 1) / BM) * (N / BN);
-    if (fd_set_max_lds((const void*)gemm_nt_kernel, 4 * TILE_BYTES) != FEDDAT_OK) return FEDDAT_ELAUNCH;
-    hipLaunchKernelGGL(gemm_nt_kernel, dim3(tiles), dim3(256), 4 * TILE_BYTES, stream, g);
-    FD_LAUNCH_RET();
+    return gemm_launch_persistent(g, r, FEDDAT_GEMM_OP16, variant, 0, grid, stream);
 }

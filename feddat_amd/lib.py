@@ -24,6 +24,8 @@ OPERAND_DTYPE = {"bf16": torch.bfloat16, "f16": torch.float16}
 EPI_BF16, EPI_RESID_F32, EPI_GELU, EPI_MUL_DGELU, EPI_F32, EPI_GELU_G8, EPI_MUL_G8, EPI_GELU_G8_F8, EPI_MUL_G8_F8 = range(9)
 F8_ACT_SCALE, F8_GRAD_HEADROOM = 0.125, 4.0      # FEDDAT_F8_ACT_SCALE / FEDDAT_F8_GRAD_HEADROOM
 G8_LO, G8_STEP = -0.135, 0.005        # FEDDAT_G8_LO / FEDDAT_G8_STEP: gelu' ~ G8_LO + G8_STEP * code
+GEMM_OP16, GEMM_FP8, GEMM_FP8MX = range(3)                               # feddat_gemm_route: operand kind
+GEMM_V1, GEMM_MID, GEMM_V2, GEMM_V3, GEMM_DUAL = range(5)                # ... and kernel family (FEDDAT_GEMM_*)
 
 ABI_VERSION = 8
 vp, i32, i64, f32, u32 = C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_uint
@@ -74,6 +76,11 @@ class AdamwGroup(C.Structure):       # feddat_adamw_group
                 ("restore_if", vp)]
 
 
+class GemmRoute(C.Structure):       # feddat_gemm_route_t
+    _fields_ = [(n, C.c_int) for n in ("family", "rows", "threads", "lds_bytes", "grid", "bm", "tiles_m", "nx", "tm_per", "tn_per",
+                                       "dbg")]
+
+
 HT_PRO_NONE, HT_PRO_LN, HT_PRO_TANH_BWD = 0, 1, 2
 HT_EPI_NONE, HT_EPI_TANH, HT_EPI_MUL_DGELU = 0, 1, 2
 
@@ -103,6 +110,7 @@ _SIGS = {
     "feddat_gemm_bf16_nt": [vp, i32, vp, i32, i32, i32, i32, i32, vp, vp, i32, vp, i32, vp, i32, vp, i32, vp, i32, vp],
     "feddat_gemm_skinny_workspace_elems": [i32, i32, i32],
     "feddat_gemm_dual_blocks_per_cu": [vp],
+    "feddat_gemm_route": [i32, i32, i32, i32, i32, i32, i32, C.POINTER(GemmRoute)],
     "feddat_gemm_fp8_nt": [vp, i32, vp, vp, i32, vp, i32, i32, i32, i32, vp, vp, i32, vp, i32, vp, i32, vp],
     "feddat_layernorm_bwd_dx_fp8": [vp, vp, i64, vp, i64, vp, vp, vp, i64, i32, i32, vp, i64, vp, vp, vp],
     "feddat_gemm_fp8mx_nt": [vp, i32, vp, i32, vp, i32, vp, i32, i32, i32, vp, vp, i32, vp],
@@ -273,7 +281,8 @@ def set_debug_flags(flags: int):
     """Kernel-selection switches (bit-identical results, except dQ of the two-role attention backward that flag 2 selects at
     S <= 192: equally accurate, not bit-identical; its dK | dV are): 1 / 2 GEMMs on the two-group / one-wave-per-SIMD kernel, 32 / 64
     force 192- / 256-row tiles, 128 no small-tile kernel, 256 K = 32 fp8 MFMA, bit 23 one attention-backward block per pair,
-    bits 28..31 cap the persistent GEMM grid.  The timing-only ablations (8 skip epilogue, 4 / 16, 512, bits 8..22, 24..26)
+    bits 28..31 cap the persistent GEMM grid, 1 | 2 together the dual form of the persistent GEMM (what they do to a given
+    GEMM launch: gemm_route).  The timing-only ablations (8 skip epilogue, 4 / 16, 512, bits 8..22, 24..26)
     exist in the ablation build only (use_ablation_build)."""
     _chk(load().feddat_set_debug_flags(int(flags)), "feddat_set_debug_flags")
 
@@ -308,6 +317,15 @@ def gemm_dual_blocks_per_cu() -> int:
     n = C.c_int(0)
     _chk(load().feddat_gemm_dual_blocks_per_cu(C.byref(n)), "feddat_gemm_dual_blocks_per_cu")
     return n.value
+
+
+def gemm_route(M: int, N: int, K: int, epi: int, *, n_cu: int, kind: int = GEMM_OP16, flags: int = 0) -> dict:
+    """The route gemm_bf16_nt (kind GEMM_OP16), gemm_fp8_nt / _f32 (GEMM_FP8) or gemm_fp8mx_nt (GEMM_FP8MX) gives this product on
+    a device of n_cu compute units under the selection flags `flags`: kernel family (GEMM_V1 .. GEMM_DUAL), tile rows, launch
+    geometry and tiling (feddat_gemm_route).  Host only: needs no device.  Raises where the entry point rejects the shape."""
+    r = GemmRoute()
+    _chk(load().feddat_gemm_route(M, N, K, epi, kind, n_cu, flags, C.byref(r)), "feddat_gemm_route")
+    return {n: getattr(r, n) for n, _ in GemmRoute._fields_}
 
 
 def rccl_available() -> bool:

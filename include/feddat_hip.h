@@ -74,7 +74,8 @@ int feddat_set_debug_flags(int flags);
  * Requirements: K % 64 == 0, lda/ldb % 8 == 0, and N % 192 == 0 with M >= 1024 (the two persistent kernels, 192 x 192 or
  * 256 x 192 tiles chosen per shape: one wave per SIMD with AGPR-pinned accumulators for the plain / residual epilogues, two
  * ping-pong wave groups for the GELU and gelu' epilogues; bit-identical results) or else N % 128 == 0 (128 x 128 kernel),
- * or M < 1024 with N % 64 == 0 (64 x 64 small-tile kernel).  Row strides (lda, ldr, ldo*) are in elements
+ * or M < 1024 with N % 64 == 0 (64 x 64 small-tile kernel; also M < 4096 with too few 192-row tiles to fill the device --
+ * feddat_gemm_route below answers which kernel and tiling a shape gets).  Row strides (lda, ldr, ldo*) are in elements
  * and may exceed the row length (strided operands).
  * ------------------------------------------------------------------------------------------- */
 #define FEDDAT_EPI_BF16 0       /* out_bf16 = acc + bias                                    */
@@ -143,6 +144,27 @@ long feddat_gemm_skinny_workspace_elems(int M, int N, int K);
 /* ABI 8, diagnostics: workgroups per CU the runtime grants the DUAL form of the persistent GEMM (two independent 128 x 192
  * workgroups per CU, 80 KiB of LDS and 256 registers per wave each; feddat_set_debug_flags 1 | 2 [| 64]) on the current device. */
 int feddat_gemm_dual_blocks_per_cu(int* out);
+/* Addition within ABI 8, host only (touches no device): the route feddat_gemm_bf16_nt (kind FEDDAT_GEMM_OP16), feddat_gemm_fp8_nt /
+ * _f32 (FEDDAT_GEMM_FP8) or feddat_gemm_fp8mx_nt (FEDDAT_GEMM_FP8MX) gives an M x N x K product (elements of that operand type)
+ * with epilogue `epi` on a device of n_cu compute units under the selection flags `flags` (feddat_set_debug_flags; 0 in
+ * production): the kernel family, its tile rows, launch geometry and the tiling the persistent kernels are handed.  It is the
+ * function those entry points call (csrc/gemm_route.h).  FEDDAT_EINVAL where they reject the shape or epilogue. */
+#define FEDDAT_GEMM_OP16 0
+#define FEDDAT_GEMM_FP8 1
+#define FEDDAT_GEMM_FP8MX 2
+#define FEDDAT_GEMM_V1 0     /* 128 x 128 tiles, one per workgroup */
+#define FEDDAT_GEMM_MID 1    /* 64 x 64 small-tile kernel */
+#define FEDDAT_GEMM_V2 2     /* persistent, two wave groups per SIMD */
+#define FEDDAT_GEMM_V3 3     /* persistent, one wave per SIMD */
+#define FEDDAT_GEMM_DUAL 4   /* v3 as two independent 128-row workgroups per CU */
+typedef struct feddat_gemm_route_t {
+    int family;                           /* FEDDAT_GEMM_V1 .. _DUAL */
+    int rows;                             /* tile height the kernel is built for: 64 (mid), 128 (v1, dual), 160 .. 256 */
+    int threads, lds_bytes, grid;         /* workgroup size, dynamic LDS, workgroups */
+    int bm, tiles_m, nx, tm_per, tn_per;  /* persistent families: rows per M tile (<= rows), M tiles, XCD split and tiles per XCD */
+    int dbg;                              /* the flags value the kernel sees */
+} feddat_gemm_route_t;
+int feddat_gemm_route(int M, int N, int K, int epi, int kind, int n_cu, int flags, feddat_gemm_route_t* out);
 int feddat_gemm_bf16_nt_skinny(const void* A, int lda, const void* B, int ldb, int M, int N, int K, int epi,
                                const float* bias, const float* resid, int ldr, const void* aux, int ldaux,
                                float* out_f32, int ldo32, void* out_bf16, int ldo16, void* out2_bf16, int ldo2,

@@ -59,7 +59,7 @@ def test_probe_tr16_layout(L):
                                    (100, 192, 128), (96, 30592, 768),     # ... N % 128 != 0; the LM-head product
                                    (1200, 256, 192), (1030, 640, 64),     # M >= 1024, N % 192 != 0: the 128 x 128 kernel
                                    (5920, 768, 3072), (11840, 2304, 768),
-                                   (11840, 3072, 768),    # the only production shape on the 256 x 192 (WM = 4) tiles
+                                   (11840, 3072, 768),    # ViLT's only production shape on the 256 x 192 (WM = 4) tiles (test_gemm_route_cpu.py)
                                    (11849, 3072, 768)])   # the same plan with a ragged last M tile
 def test_gemm_epilogues(L, M, N, K):
     g = torch.Generator(device="cpu").manual_seed(M + N + K)

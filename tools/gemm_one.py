@@ -1,5 +1,6 @@
 #!/usr/bin/env python
-"""One K1 launch shape for counter collection: python tools/gemm_one.py M N K epi flags [reps]"""
+"""One K1 launch shape for counter collection: python tools/gemm_one.py M N K epi flags [reps]
+Prints the route of the launch it times (kernel family, tile rows, grid, LDS, tiling: lib.gemm_route)."""
 import os
 import sys
 
@@ -21,6 +22,7 @@ aux = torch.randn(M, N, device=dev).bfloat16()
 resid = torch.randn(M, N, device=dev)
 bias = torch.randn(N, device=dev)
 L.set_debug_flags(flags)
+print("route:", L.gemm_route(M, N, K, epi, n_cu=torch.cuda.get_device_properties(0).multi_processor_count, flags=flags), flush=True)
 for _ in range(reps):
     if epi == 0:
         L.gemm_bf16_nt(A, B, 0, bias=bias, out_bf16=o)
