@@ -660,7 +660,10 @@ __global__ void single_step_finish_kernel(const SingleFinish s, int* flag, float
     *flag = 0;
 }
 
-int ht_fill(HtJob& j, const feddat_ht_job& s) {
+// Every decision feddat_head_gemm takes about one job, and every reason it refuses one: host arithmetic on the job's sizes,
+// strides and pointer VALUES only (nothing is dereferenced, no device is touched), exported as feddat_head_gemm_plan and
+// pinned on the CPU by tests/test_head_gemm_plan_cpu.py.  ht_fill below is its only other caller.
+int ht_plan(const feddat_ht_job& s, feddat_ht_plan& p) {
     if (!(s.A && s.B && s.out && s.I > 0 && s.J > 0 && s.K > 0 && s.ldo >= s.J && (s.mode == 0 || s.mode == 1)))
         return FEDDAT_EINVAL;
     if (s.pro == FEDDAT_HT_PRO_LN && !(s.pro_a && s.pro_b && s.pro_eps > 0.f && s.sa_k == 1 && s.K % 4 == 0 && s.K <= 2048 &&
@@ -669,22 +672,31 @@ int ht_fill(HtJob& j, const feddat_ht_job& s) {
     if (s.pro == FEDDAT_HT_PRO_TANH_BWD && !s.pro_a) return FEDDAT_EINVAL;
     if (s.epi == FEDDAT_HT_EPI_MUL_DGELU && !(s.aux && s.ld_aux >= s.J)) return FEDDAT_EINVAL;
     if (s.pro < 0 || s.pro > FEDDAT_HT_PRO_TANH_BWD || s.epi < 0 || s.epi > FEDDAT_HT_EPI_MUL_DGELU) return FEDDAT_EINVAL;
+    p.avec = s.sa_k == 1 && s.K % 4 == 0 && s.sa_i % 4 == 0 && ((uintptr_t)s.A & 15) == 0 &&
+             (s.pro != FEDDAT_HT_PRO_TANH_BWD || ((uintptr_t)s.pro_a & 15) == 0);
+    p.bvec = s.sb_k == 1 && s.K % 4 == 0 && s.sb_j % 4 == 0 && ((uintptr_t)s.B & 15) == 0;
+    if (s.pro == FEDDAT_HT_PRO_LN && !(p.avec && (((uintptr_t)s.pro_a | (uintptr_t)s.pro_b) & 15) == 0)) return FEDDAT_EINVAL;
+    p.itiles = (s.I + 15) / 16;
+    int jgroups = (s.J + 16 * HT_JT - 1) / (16 * HT_JT);
+    p.jt = HT_JT;
+    if (s.mode == 0 && p.itiles * jgroups < 64) {      // too few 16 x 64 tiles: 16 x 16 tiles, four times the blocks
+        p.jt = 1;
+        jgroups = (s.J + 15) / 16;
+    }
+    p.jblocks = s.mode == 0 ? jgroups : (jgroups + HT_NW - 1) / HT_NW;
+    p.blocks = p.itiles * p.jblocks;
+    return FEDDAT_OK;
+}
+
+int ht_fill(HtJob& j, const feddat_ht_job& s) {
+    feddat_ht_plan p;
+    const int rc = ht_plan(s, p);
+    if (rc != FEDDAT_OK) return rc;
     j.A = s.A; j.sa_i = s.sa_i; j.sa_k = s.sa_k; j.B = s.B; j.sb_k = s.sb_k; j.sb_j = s.sb_j;
     j.I = s.I; j.J = s.J; j.K = s.K; j.mode = s.mode; j.alpha = s.alpha; j.alpha_dev = s.alpha_dev; j.bias_j = s.bias_j; j.out = s.out; j.ldo = s.ldo;
     j.colsum = s.colsum; j.pro = s.pro; j.pro_a = s.pro_a; j.pro_b = s.pro_b; j.pro_eps = s.pro_eps;
     j.stats_out = s.stats_out; j.epi = s.epi; j.aux = s.aux; j.ld_aux = s.ld_aux;
-    j.avec = s.sa_k == 1 && s.K % 4 == 0 && s.sa_i % 4 == 0 && ((uintptr_t)s.A & 15) == 0 &&
-             (s.pro != FEDDAT_HT_PRO_TANH_BWD || ((uintptr_t)s.pro_a & 15) == 0);
-    j.bvec = s.sb_k == 1 && s.K % 4 == 0 && s.sb_j % 4 == 0 && ((uintptr_t)s.B & 15) == 0;
-    if (s.pro == FEDDAT_HT_PRO_LN && !(j.avec && (((uintptr_t)s.pro_a | (uintptr_t)s.pro_b) & 15) == 0)) return FEDDAT_EINVAL;
-    j.itiles = (s.I + 15) / 16;
-    int jgroups = (s.J + 16 * HT_JT - 1) / (16 * HT_JT);
-    j.jt = HT_JT;
-    if (s.mode == 0 && j.itiles * jgroups < 64) {      // too few 16 x 64 tiles: 16 x 16 tiles, four times the blocks
-        j.jt = 1;
-        jgroups = (s.J + 15) / 16;
-    }
-    j.jblocks = s.mode == 0 ? jgroups : (jgroups + HT_NW - 1) / HT_NW;
+    j.avec = p.avec; j.bvec = p.bvec; j.jt = p.jt; j.itiles = p.itiles; j.jblocks = p.jblocks;
     return FEDDAT_OK;
 }
 
@@ -705,6 +717,11 @@ extern "C" int feddat_head_gemm(const feddat_ht_job* jobs, int njobs, hipStream_
     if (fd_set_max_lds((const void*)ht_gemm_kernel, lds) != FEDDAT_OK) return FEDDAT_ELAUNCH;
     hipLaunchKernelGGL(ht_gemm_kernel, dim3(total), dim3(HT_NW * 64), lds, stream, L);
     FD_LAUNCH_RET();
+}
+
+extern "C" int feddat_head_gemm_plan(const feddat_ht_job* job, feddat_ht_plan* out) {
+    FD_CHECK_ARG(job && out);
+    return ht_plan(*job, *out);
 }
 
 extern "C" int feddat_head_ln_gelu(const float* x, const float* gamma, const float* beta, float eps, int rows, int H,

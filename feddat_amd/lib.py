@@ -81,6 +81,10 @@ class GemmRoute(C.Structure):       # feddat_gemm_route_t
                                        "dbg")]
 
 
+class HtPlan(C.Structure):          # feddat_ht_plan
+    _fields_ = [(n, C.c_int) for n in ("avec", "bvec", "jt", "itiles", "jblocks", "blocks")]
+
+
 HT_PRO_NONE, HT_PRO_LN, HT_PRO_TANH_BWD = 0, 1, 2
 HT_EPI_NONE, HT_EPI_TANH, HT_EPI_MUL_DGELU = 0, 1, 2
 
@@ -166,6 +170,7 @@ _SIGS = {
     "feddat_ln_param_grad_partial": [vp, vp, i64, vp, i64, vp, i32, i32, vp, vp, i64, vp],
     "feddat_vector_grad_reduce": [vp, i32, i32, f32, vp, vp, vp],
     "feddat_head_gemm": [C.POINTER(HtJob), i32, vp],
+    "feddat_head_gemm_plan": [C.POINTER(HtJob), C.POINTER(HtPlan)],
     "feddat_head_ln_gelu": [vp, vp, vp, f32, i32, i32, vp, vp, vp, vp],
     "feddat_head_ln_bwd_full": [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp],
     "feddat_adamw_multi": [C.POINTER(AdamwGroup), i32, f32, i32, i32, f32, f32, f32, vp],
@@ -734,6 +739,15 @@ def head_gemm(*jobs: HtJob):
     arr = (HtJob * len(jobs))(*jobs)
     arr._keep = jobs
     _chk(load().feddat_head_gemm(arr, len(jobs), _stream()), "feddat_head_gemm")
+
+
+def head_gemm_plan(job: HtJob) -> dict:
+    """The path and grid feddat_head_gemm gives this job: avec / bvec (16-byte or dword loads of A / B), jt (16-column tiles per
+    wave), itiles, jblocks, blocks (feddat_head_gemm_plan).  Host only: needs no device and reads only the job's sizes, strides
+    and pointer values, so the job may hold made-up addresses.  Raises where head_gemm rejects the job."""
+    p = HtPlan()
+    _chk(load().feddat_head_gemm_plan(C.byref(job), C.byref(p)), "feddat_head_gemm_plan")
+    return {n: getattr(p, n) for n, _ in HtPlan._fields_}
 
 
 def head_ln_gelu(x, gamma, beta, eps, y, stats, gelu_out):

@@ -471,6 +471,16 @@ typedef struct feddat_ht_job {
     const float* alpha_dev;    /* ABI 8: optional DEVICE float multiplied onto alpha at run time (the dynamic loss scale) */
 } feddat_ht_job;
 int feddat_head_gemm(const feddat_ht_job* jobs, int njobs, hipStream_t stream);
+/* Which code path and grid feddat_head_gemm gives ONE job -- the function that entry point itself calls for each of its jobs.
+ * Host only: touches no device and dereferences none of the job's pointers (only their values: NULL or not, 16-byte aligned
+ * or not), so tests/test_head_gemm_plan_cpu.py pins it on a machine without a GPU.  avec / bvec: the A / B operand is fetched
+ * with 16-byte loads along k (contiguous along k, K % 4 == 0, row stride % 4 == 0, base -- and the tanh' prologue's y --
+ * 16-byte aligned), else with dword loads; jt: 16-column tiles per wave (4, or 1 for a mode-0 job of fewer than 64 16 x 64
+ * tiles); the job runs on blocks = itiles * jblocks workgroups.  FEDDAT_EINVAL exactly where feddat_head_gemm rejects the job. */
+typedef struct feddat_ht_plan {
+    int avec, bvec, jt, itiles, jblocks, blocks;
+} feddat_ht_plan;
+int feddat_head_gemm_plan(const feddat_ht_job* job, feddat_ht_plan* out);
 /* y = LayerNorm(x) (stats [rows, 2] = {mean, rstd}), gelu_out = gelu(y): clf_norm0 + clf_actv0 (vilt.py:205-206) */
 int feddat_head_ln_gelu(const float* x, const float* gamma, const float* beta, float eps, int rows, int H, float* y,
                         float* stats, float* gelu_out, hipStream_t stream);
