@@ -455,6 +455,147 @@ __global__ __launch_bounds__(1024) void dat_loss_rows_kernel(const float* __rest
     dat_loss_single_body(logits, teacher, target, n, C, temp, dlogits, scalars, nonfinite);
 }
 
+// DAT loss at ANY width (the reference's `vqa` task: num_labels = 3129, task_configs_fed.py; same formulas and outputs as
+// dat_loss_single_body): one workgroup of 256 threads per row of the B-row frame, thread t takes columns t, t + 256, ...
+// Rows [0, n) are the batch; a workgroup of a row in [n, B) writes its dlogits row as 0.0f and reads nothing.  Up to
+// WIDE_REG_C = 256 * WIDE_NPT = 4096 columns the row's three operands are loaded once and stay in registers over the three
+// passes (maxima; sums of exponentials; terms and dlogits): 3 * 16 = 48 operand VGPRs per lane, nothing spills; wider rows
+// re-read their operands in every pass.  Every load is a dword (a row of 3129 floats starts 16-byte aligned only every fourth
+// row); consecutive lanes read consecutive floats.  Reductions in a fixed order, no float atomics: wave_max / wave_sum, then the
+// row's waves 0..3 in that order through LDS.  The row's two terms go to workspace[2 b], workspace[2 b + 1]; the batch sums
+// are dat_loss_wide_finish_kernel, a second launch.
+constexpr int WIDE_T = 256;
+constexpr int WIDE_NPT = 16;
+constexpr int WIDE_REG_C = WIDE_T * WIDE_NPT;
+
+__device__ __forceinline__ void wide_row_max2(float& a, float& b, float (*part)[4]) {
+    a = wave_max(a);
+    b = wave_max(b);
+    if ((threadIdx.x & 63) == 0) {
+        part[0][threadIdx.x >> 6] = a;
+        part[1][threadIdx.x >> 6] = b;
+    }
+    __syncthreads();
+    a = fmaxf(fmaxf(fmaxf(part[0][0], part[0][1]), part[0][2]), part[0][3]);
+    b = fmaxf(fmaxf(fmaxf(part[1][0], part[1][1]), part[1][2]), part[1][3]);
+}
+
+__device__ __forceinline__ void wide_row_sum2(float& a, float& b, float (*part)[4]) {
+    a = wave_sum(a);
+    b = wave_sum(b);
+    if ((threadIdx.x & 63) == 0) {
+        part[0][threadIdx.x >> 6] = a;
+        part[1][threadIdx.x >> 6] = b;
+    }
+    __syncthreads();
+    a = ((part[0][0] + part[0][1]) + part[0][2]) + part[0][3];
+    b = ((part[1][0] + part[1][1]) + part[1][2]) + part[1][3];
+}
+
+// one element's BCE and KL terms and its dlogits (the arithmetic of dat_loss_single_body, element by element)
+__device__ __forceinline__ float wide_elem(float x, float t, float y, float it, float temp, float lsx, float lst, float gs,
+                                           float& bce, float& kl) {
+    bce += fmaxf(x, 0.f) - x * y + log1pf(expf(-fabsf(x)));
+    const float logp = x * it - lsx;
+    const float logq = t * it - lst;
+    const float q = expf(logq);
+    kl += q * (logq - logp);
+    const float sig = 1.0f / (1.0f + expf(-x));
+    return gs * ((sig - y) + temp * (expf(logp) - q));
+}
+
+template <bool REG>
+__global__ __launch_bounds__(WIDE_T) void dat_loss_wide_kernel(const float* __restrict__ logits,
+                                                               const float* __restrict__ teacher,
+                                                               const float* __restrict__ target, int n, int C, float temp,
+                                                               float* __restrict__ dlogits, float* __restrict__ row_terms) {
+    __shared__ float part[3][2][4];       // one slot per pass: one barrier per pass
+    const int b = blockIdx.x, tid = threadIdx.x;
+    float* __restrict__ dl = dlogits + (size_t)b * C;
+    if (b >= n) {       // a replica row of a short batch: zero gradient, its inputs are never read
+        for (int j = tid; j < C; j += WIDE_T) dl[j] = 0.0f;
+        return;
+    }
+    const float* __restrict__ x = logits + (size_t)b * C;
+    const float* __restrict__ t = teacher + (size_t)b * C;
+    const float* __restrict__ y = target + (size_t)b * C;
+    const float it = 1.0f / temp, gs = 0.5f / (float)n;
+    float mx = -INFINITY, mt = -INFINITY, sx = 0.f, st = 0.f, bce = 0.f, kl = 0.f;
+    if (REG) {
+        float xv[WIDE_NPT], tv[WIDE_NPT], yv[WIDE_NPT];
+#pragma unroll
+        for (int k = 0; k < WIDE_NPT; ++k) {
+            const int j = tid + WIDE_T * k;
+            const bool ok = j < C;
+            xv[k] = ok ? x[j] : 0.f;
+            tv[k] = ok ? t[j] : 0.f;
+            yv[k] = ok ? y[j] : 0.f;
+        }
+#pragma unroll
+        for (int k = 0; k < WIDE_NPT; ++k) {
+            if (tid + WIDE_T * k < C) {
+                mx = fmaxf(mx, xv[k] * it);
+                mt = fmaxf(mt, tv[k] * it);
+            }
+        }
+        wide_row_max2(mx, mt, part[0]);
+#pragma unroll
+        for (int k = 0; k < WIDE_NPT; ++k) {
+            if (tid + WIDE_T * k < C) {
+                sx += expf(xv[k] * it - mx);
+                st += expf(tv[k] * it - mt);
+            }
+        }
+        wide_row_sum2(sx, st, part[1]);
+        const float lsx = mx + logf(sx), lst = mt + logf(st);
+#pragma unroll
+        for (int k = 0; k < WIDE_NPT; ++k) {
+            const int j = tid + WIDE_T * k;
+            if (j < C) dl[j] = wide_elem(xv[k], tv[k], yv[k], it, temp, lsx, lst, gs, bce, kl);
+        }
+    } else {
+        for (int j = tid; j < C; j += WIDE_T) {
+            mx = fmaxf(mx, x[j] * it);
+            mt = fmaxf(mt, t[j] * it);
+        }
+        wide_row_max2(mx, mt, part[0]);
+        for (int j = tid; j < C; j += WIDE_T) {
+            sx += expf(x[j] * it - mx);
+            st += expf(t[j] * it - mt);
+        }
+        wide_row_sum2(sx, st, part[1]);
+        const float lsx = mx + logf(sx), lst = mt + logf(st);
+        for (int j = tid; j < C; j += WIDE_T) dl[j] = wide_elem(x[j], t[j], y[j], it, temp, lsx, lst, gs, bce, kl);
+    }
+    wide_row_sum2(bce, kl, part[2]);
+    if (tid == 0) {
+        row_terms[2 * b] = bce;
+        row_terms[2 * b + 1] = kl;
+    }
+}
+
+// The batch sums of the wide loss, one wave, in the order of dat_loss_finish (loss_optim.hip): lane b % 64 adds its rows in row
+// order, then wave_sum; + GradScaler's inf check of the loss.  A launch of its own on purpose: the hand-off from the row
+// workgroups is the kernel boundary, not a fence and a ticket across XCDs.
+__global__ __launch_bounds__(64) void dat_loss_wide_finish_kernel(const float* __restrict__ row_terms, int n, float temp,
+                                                                  float* __restrict__ scalars, int* __restrict__ nonfinite) {
+    float bce = 0.f, kl = 0.f;
+    for (int b = threadIdx.x; b < n; b += 64) {
+        bce += row_terms[2 * b];
+        kl += row_terms[2 * b + 1];
+    }
+    bce = wave_sum(bce);
+    kl = wave_sum(kl);
+    if (threadIdx.x == 0) {
+        const float l_bce = bce / (float)n;
+        const float l_kl = kl / (float)n * temp * temp;
+        scalars[0] = l_bce;
+        scalars[1] = l_kl;
+        scalars[2] = 0.5f * (l_bce + l_kl);
+        if (nonfinite && fd_nonfinite(l_bce + l_kl)) atomicOr(nonfinite, 1);
+    }
+}
+
 // Single-adapter step loss (optimizer_mode adapter; task_trainer.py:433-441): L = BCEWithLogits_mean(logits, target) * C and
 // dL/dlogits = (sigmoid(x) - t) / B in ONE launch.  Any C: lane j of a wave takes columns j, j + 64, ...; for C <= 128 a row's
 // terms are added in dat_loss_single_kernel's order and its batch sum is the same, so scalars[0] carries the same bits as
@@ -763,6 +904,23 @@ extern "C" int feddat_dat_loss_fwd_bwd_rows(const float* logits, const float* te
                  temp > 0.f);
     hipLaunchKernelGGL(dat_loss_rows_kernel, dim3(1), dim3(1024), 2 * n * sizeof(float), stream, logits, teacher, target, n, B,
                        C, temp, dlogits, scalars, nonfinite);
+    FD_LAUNCH_RET();
+}
+
+extern "C" long feddat_dat_loss_wide_workspace_elems(int B) { return B > 0 ? 2L * B : 0L; }
+
+extern "C" int feddat_dat_loss_fwd_bwd_wide(const float* logits, const float* teacher, const float* target, int n, int B, int C,
+                                            float temp, float* dlogits, float* scalars, int* nonfinite, float* workspace,
+                                            long workspace_elems, hipStream_t stream) {
+    FD_CHECK_ARG(logits && teacher && target && dlogits && scalars && workspace && n > 0 && n <= B && B <= 4096 && C > 0 &&
+                 temp > 0.f && workspace_elems >= feddat_dat_loss_wide_workspace_elems(B));
+    if (C <= WIDE_REG_C)
+        hipLaunchKernelGGL(dat_loss_wide_kernel<true>, dim3(B), dim3(WIDE_T), 0, stream, logits, teacher, target, n, C, temp,
+                           dlogits, workspace);
+    else
+        hipLaunchKernelGGL(dat_loss_wide_kernel<false>, dim3(B), dim3(WIDE_T), 0, stream, logits, teacher, target, n, C, temp,
+                           dlogits, workspace);
+    hipLaunchKernelGGL(dat_loss_wide_finish_kernel, dim3(1), dim3(64), 0, stream, workspace, n, temp, scalars, nonfinite);
     FD_LAUNCH_RET();
 }
 

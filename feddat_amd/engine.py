@@ -139,6 +139,8 @@ class ViltDatEngine(ViltBackbone):
         # pass ("all" = rows [0,B), "p1" = rows [B,2B) of the "both" buffers); P2 uses the updated head.
         self.hd["p2"] = dict(a0=f32(B, 2 * H), n0=f32(B, 2 * H), st=f32(B, 2), g0=f32(B, 2 * H), logits=f32(B, self.C))
         self.loss_buf = {k: f32(4 + 2 * B) for k in ("p1", "p2")}
+        # row terms of the any-width DAT loss (heads of more than 128 labels: feddat_dat_loss_fwd_bwd_wide), at a static address
+        self.loss_ws = f32(L.dat_loss_wide_workspace_elems(B))
         self.z = f32(R2, self.r)
         self.dz = f32(R2, self.r)
         # relu(W_down h3 + b_down) of every adapter slot, saved by the adapter forward of each layer for its backward
@@ -558,7 +560,11 @@ class ViltDatEngine(ViltBackbone):
         return [("adapter_0", self.ad[0]), ("adapter_1", self.ad[1]), ("head", self.head[self.task])]
 
     def _loss(self, logits, teacher, slot):
-        if self.n_valid < self.B:      # a short batch: the loss of the n valid rows, zero gradient in the replica rows
+        if self.C > 128:      # the one-launch forms below hold a row in two elements per lane; wider heads (vqa: 3129 labels)
+            flag = (self.ovf_flags[1:2] if slot == "p1" else self.ovf_flags[0:1]) if self._dyn() else None
+            L.dat_loss_fwd_bwd_wide(logits, teacher, self.inp["target"], self.dlogits, self.loss_buf[slot], self.loss_ws,
+                                    n=self.n_valid, nonfinite=flag)
+        elif self.n_valid < self.B:      # a short batch: the loss of the n valid rows, zero gradient in the replica rows
             flag = self.ovf_flags[1:2] if slot == "p1" else self.ovf_flags[0:1]
             L.dat_loss_fwd_bwd_rows(logits, teacher, self.inp["target"], self.dlogits, self.loss_buf[slot], self.n_valid,
                                     flag if self._dyn() else None)

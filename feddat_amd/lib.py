@@ -165,6 +165,8 @@ _SIGS = {
     "feddat_single_step_finish": [C.POINTER(vp), i32, vp, vp, vp, f32, f32, i32, vp],
     "feddat_dat_loss_fwd_bwd_rows": [vp, vp, vp, i32, i32, i32, f32, vp, vp, vp, vp],
     "feddat_bce_loss_fwd_bwd_rows": [vp, vp, i32, i32, i32, vp, vp, vp, vp],
+    "feddat_dat_loss_wide_workspace_elems": [i32],
+    "feddat_dat_loss_fwd_bwd_wide": [vp, vp, vp, i32, i32, i32, f32, vp, vp, vp, vp, i64, vp],
     "feddat_vector_grad_workspace_elems": [i32, i32],
     "feddat_colsum_partial": [vp, vp, i64, vp, i32, i32, vp, i64, vp],
     "feddat_ln_param_grad_partial": [vp, vp, i64, vp, i64, vp, i32, i32, vp, vp, i64, vp],
@@ -805,6 +807,28 @@ def dat_loss_fwd_bwd_rows(logits, teacher, target, dlogits, scalars, n, nonfinit
     assert logits.shape[0] >= n and teacher.shape[0] >= n and target.shape[0] >= n and logits.shape[1] == Cn
     _chk(load().feddat_dat_loss_fwd_bwd_rows(_p(logits), _p(teacher), _p(target), int(n), B, Cn, temp, _p(dlogits), _p(scalars),
                                              _p(nonfinite), _stream()), "feddat_dat_loss_fwd_bwd_rows")
+
+
+def dat_loss_wide_workspace_elems(B: int) -> int:
+    """Floats of the row-term workspace dat_loss_fwd_bwd_wide needs for a B-row frame (2 B)."""
+    return int(load().feddat_dat_loss_wide_workspace_elems(int(B)))
+
+
+def dat_loss_fwd_bwd_wide(logits, teacher, target, dlogits, scalars, workspace, n=None, nonfinite=None, temp=3.0):
+    """The DAT loss at any width (include/feddat_hip.h: feddat_dat_loss_fwd_bwd_wide): rows [0, n) of the B-row frame
+    (B = dlogits.shape[0]; n = None: all of them), dlogits[n:] = 0; nonfinite (int32 device tensor, optional) gets 1 OR-ed in
+    when the loss is inf / NaN; workspace: fp32 device tensor of at least dat_loss_wide_workspace_elems(B) elements."""
+    _dev(logits, teacher, target, dlogits, scalars, workspace, nonfinite)
+    B, Cn = dlogits.shape
+    n = B if n is None else int(n)
+    assert scalars.numel() >= 4 and (nonfinite is None or nonfinite.dtype == torch.int32)
+    assert workspace.dtype == torch.float32 and workspace.is_contiguous()
+    for t in (logits, teacher, target, dlogits):      # the kernel indexes all four as [b * C + j]
+        assert t.dtype == torch.float32 and t.dim() == 2 and t.is_contiguous() and t.shape[1] == Cn and t.shape[0] >= n
+    assert scalars.dtype == torch.float32 and scalars.is_contiguous() and 1 <= n <= B
+    _chk(load().feddat_dat_loss_fwd_bwd_wide(_p(logits), _p(teacher), _p(target), n, B, Cn, temp, _p(dlogits), _p(scalars),
+                                             _p(nonfinite), _p(workspace), workspace.numel(), _stream()),
+         "feddat_dat_loss_fwd_bwd_wide")
 
 
 def bce_loss_fwd_bwd_rows(logits, target, dlogits, scalars, n, nonfinite=None):

@@ -43,11 +43,15 @@ class FlatGroup:
             self.offsets[n] = off
             off += int(math.prod(s))
         self.numel = off
-        self.p = torch.zeros(off, device=device)
+        # the buffers hold a whole number of quads (the multi-group AdamW moves 16 bytes per lane: feddat_adamw_multi wants
+        # n % 4 == 0); up to 3 floats behind the last tensor (a head of 3129 labels: 5 993 529 floats) stay 0.0f for good --
+        # zero gradient, zero moments, and they belong to no name
+        alloc = (off + 3) // 4 * 4
+        self.p = torch.zeros(alloc, device=device)
         if with_opt:
-            self.g = torch.zeros(off, device=device)
-            self.m = torch.zeros(off, device=device)
-            self.v = torch.zeros(off, device=device)
+            self.g = torch.zeros(alloc, device=device)
+            self.m = torch.zeros(alloc, device=device)
+            self.v = torch.zeros(alloc, device=device)
             offs = [self.offsets[n] for n in self.names] + [off]
             self.seg_off = torch.tensor(offs, dtype=torch.int64, device=device)
             self.seg_wd = torch.tensor([0.0 if _no_decay(n) else 1.0 for n in self.names], device=device)
@@ -291,7 +295,8 @@ class LocalUpdateEngine:
 
     def comm_flat(self) -> torch.Tensor:
         """The FedAvg payload: every tensor of the averaged adapter back-to-back in state-dict order (main.py:154-163,499-503)."""
-        return self.ad[self.COMM_ADAPTER].p
+        grp = self.ad[self.COMM_ADAPTER]
+        return grp.p[:grp.numel]      # without FlatGroup's quad padding (the adapters' sizes are multiples of 4: the whole buffer)
 
     def comm_written(self):
         """To be called after comm_flat() was overwritten (a server copy, the FedAvg write-back): rebuilds what the step derives

@@ -197,8 +197,10 @@ class ViltContinualLearner:
 
     def __init__(self, ordered_cl_tasks: List[str], params: Dict[str, torch.Tensor], device, batch_size: int,
                  image_size: int = 384, num_layers: int = 12, lr: float = 1e-4, vocab=None, operands: str = None,
-                 optimizer_mode: str = "dat"):
-        """operands: 16-bit MFMA operand format of the engine, "f16" (default; the reference's mixed_precision: fp16,
+                 optimizer_mode: str = "dat", num_labels: int = 100):
+        """num_labels: width of every task head (task_configs_fed.py: 100 for the CLOVE / domain tasks, 3129 for vqa; one engine
+        has one width).
+        operands: 16-bit MFMA operand format of the engine, "f16" (default; the reference's mixed_precision: fp16,
         accelerate_config.yaml:8) or "bf16" (engine.ViltDatEngine).
         optimizer_mode: "dat" (adapter_{0,1,2}, engine.ViltDatEngine) or "adapter" (the FedAvg baseline: one adapter per
         layer, adapter_engine.ViltAdapterEngine; main.py:114-118,141-149), "bias" or "norm" (the plain backbone with every
@@ -219,7 +221,8 @@ class ViltContinualLearner:
         else:
             raise L.FeddatHipError(f"optimizer_mode must be one of {MODES}, got {optimizer_mode!r}")
         self.engine = Engine(params, self.ordered_cl_tasks, self.device, batch=batch_size, res=image_size, layers=num_layers,
-                             lr=lr, operands=operands)
+                             lr=lr, operands=operands, num_labels=num_labels)
+        self.num_labels = int(num_labels)
         self.max_text_length = self.engine.Lt               # vilt.py:50: config.max_position_embeddings = 40
         self._vocab = vocab
         self._tokenizer = None
@@ -329,11 +332,11 @@ class ViltContinualLearner:
 def create_vilt_continual_learner_model(params: Dict[str, torch.Tensor], ordered_cl_tasks: List[str], device,
                                         batch_size: int, image_size: int = 384, num_layers: int = 12,
                                         lr: float = 1e-4, vocab=None, operands: str = None,
-                                        optimizer_mode: str = "dat") -> ViltContinualLearner:
+                                        optimizer_mode: str = "dat", num_labels: int = 100) -> ViltContinualLearner:
     """vilt.py:421-452 (the pretrained checkpoint is passed in as a tensor dict: feddat_amd.weights.load_vilt_pretrained
     reads it from a local HF directory; there is no hub access here)."""
     return ViltContinualLearner(ordered_cl_tasks, params, device, batch_size, image_size, num_layers, lr, vocab=vocab,
-                                operands=operands, optimizer_mode=optimizer_mode)
+                                operands=operands, optimizer_mode=optimizer_mode, num_labels=num_labels)
 
 
 def convert_batch_to_vilt_input_dict(batch: Dict):

@@ -360,6 +360,16 @@ TASK_SETS = {   # main.py:352-359
 }
 
 
+def federation_num_labels(tasks: Sequence[str]) -> int:
+    """Head width of a ViLT federation: the label count the reference's task table gives its tasks (vilt_spec.TASK_NUM_LABELS;
+    100 for a name it does not hold).  One engine has one width, so tasks of different widths are refused."""
+    widths = {t: vilt_spec.task_num_labels(t) for t in tasks}
+    if len(set(widths.values())) > 1:
+        raise L.FeddatHipError(f"--ordered_cl_tasks mixes head widths {widths}: one engine has one width (num_labels), so every "
+                               "task of a federation must have the same label count")
+    return next(iter(widths.values()))
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
     mode = "dat" if "dat" in args.optimizer_mode else args.optimizer_mode
@@ -375,6 +385,9 @@ def main(argv=None):
         if not 1 <= args.synthetic_last_batch <= args.batch_size:
             raise L.FeddatHipError(f"--synthetic_last_batch must lie in 1 .. batch_size ({args.batch_size}), got "
                                    f"{args.synthetic_last_batch}")
+    tasks = TASK_SETS.get(args.ordered_cl_tasks, args.ordered_cl_tasks.split(","))
+    # the head width of the federation, from the reference's task table (vqa: 3129 labels); ALBEF has no answer head
+    num_labels = federation_num_labels(tasks) if "albef" not in args.encoder_name else None
     logging.basicConfig(level=logging.INFO, format="%(asctime)s - %(levelname)s - %(message)s")
     log = logging.getLogger("feddat_amd")
     if args.mixed_precision is None:       # one default, the same as bench.py's and the engines' own
@@ -396,7 +409,6 @@ def main(argv=None):
             dist.init_process_group("nccl", device_id=torch.device("cuda", local))
         else:
             dist.init_process_group(backend)
-    tasks = TASK_SETS.get(args.ordered_cl_tasks, args.ordered_cl_tasks.split(","))
     steps_list = [int(x) for x in str(args.synthetic_steps).split(",")]
     steps_of = {t: steps_list[i % len(steps_list)] for i, t in enumerate(tasks)}
     # client -> GPU mapping.  One client per rank when there are at least as many ranks as clients (rank k <-> client k);
@@ -431,14 +443,15 @@ def main(argv=None):
         Trainer = AlbefTaskTrainer
     else:
         if pretrained:       # load_vilt_encoder (vilt.py:387-420): HF directory / state dict + modality-embedding expansion
-            params = weights.load_vilt_pretrained(pretrained, tasks, layers=args.num_layers, seed=args.seed, optimizer_mode=mode)
+            params = weights.load_vilt_pretrained(pretrained, tasks, layers=args.num_layers, seed=args.seed,
+                                                  num_labels=num_labels, optimizer_mode=mode)
             log.info("loaded ViLT weights from %s", pretrained)
         else:                # no --pretrained_model_name: random weights of the real architecture (synthetic benchmarks)
-            params = vilt_spec.random_init(args.num_layers, tasks, seed=args.seed, optimizer_mode=mode)
+            params = vilt_spec.random_init(args.num_layers, tasks, seed=args.seed, optimizer_mode=mode, num_labels=num_labels)
         model = create_vilt_continual_learner_model(params, tasks, dev, args.batch_size, args.image_size,
                                                     args.num_layers, args.lr,
                                                     operands={"fp16": "f16", "bf16": "bf16"}[args.mixed_precision],
-                                                    optimizer_mode=mode)
+                                                    optimizer_mode=mode, num_labels=num_labels)
         Trainer = TaskTrainer
     eng = model.engine
     # personal parameters per client (main.py:440-450): head + adapter_0 + adapter_2 (dat) / head (adapter, bias, norm)
@@ -450,8 +463,10 @@ def main(argv=None):
         if albef:
             return albef_spec.synthetic_batch(args.batch_size, seed, image=args.image_size, vocab=dims.get("vocab", 30522),
                                               device=dev)
-        prior = vilt_spec.client_label_prior(ti, alpha=args.synthetic_label_alpha) if args.synthetic_label_alpha > 0 else None
-        return vilt_spec.synthetic_batch(n or args.batch_size, args.image_size, seed, device=dev, label_prior=prior)
+        prior = vilt_spec.client_label_prior(ti, num_labels, alpha=args.synthetic_label_alpha) \
+            if args.synthetic_label_alpha > 0 else None
+        return vilt_spec.synthetic_batch(n or args.batch_size, args.image_size, seed, device=dev, num_labels=num_labels,
+                                         label_prior=prior)
     # --synthetic_last_batch N: the last batch of every client holds N samples (len(dataset) % batch_size != 0)
     last = args.synthetic_last_batch or None
     data = {t: [make_batch(args.seed + 1000 * ti + s, ti, last if s == steps_of[t] - 1 else None) for s in range(steps_of[t])]

@@ -315,7 +315,7 @@ class ViltVectorEngine(ViltBackbone):
     def comm_flat(self) -> torch.Tensor:
         """The FedAvg payload: every trainable backbone vector back-to-back (the heads' own 'bias' / 'norm' keys are in the
         reference's communicated list too, but get_average_net skips every 'clf' key: main.py:54)."""
-        return self.vec.p
+        return self.vec.p[:self.vec.numel]      # without FlatGroup's quad padding (none at these sizes)
 
     def comm_written(self):
         """Nothing to rebuild: the kernels read the fp32 vectors in place."""

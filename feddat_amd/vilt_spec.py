@@ -10,6 +10,20 @@ import torch
 
 ENC = "vilt_encoder.vilt."
 
+# Label counts of the reference's task table (src/configs/task_configs_fed.py, 'num_labels'): every CLOVE / domain task answers
+# over 100 labels, `vqa` (VQAv2) over 3129.  A task name the table does not hold gets DEFAULT_NUM_LABELS.
+DEFAULT_NUM_LABELS = 100
+TASK_NUM_LABELS = {
+    **{t: 100 for t in ("art", "abstract", "vizwiz", "toronto", "gqa")},
+    **{f"clove_scene_{c}": 100 for c in "abcdef"},
+    **{f"clove_function_{c}": 100 for c in "abcde"},
+    "vqa": 3129,
+}
+
+
+def task_num_labels(task: str) -> int:
+    return TASK_NUM_LABELS.get(task, DEFAULT_NUM_LABELS)
+
 
 def param_shapes(layers: int = 12, tasks: Sequence[str] = ("art",), hidden: int = 768, inter: int = 3072,
                  patch: int = 32, grid: int = 12, max_text: int = 40, vocab: int = 30522, num_labels: int = 100,
@@ -67,14 +81,15 @@ def param_shapes(layers: int = 12, tasks: Sequence[str] = ("art",), hidden: int 
 
 
 def random_init(layers: int = 12, tasks: Sequence[str] = ("art",), seed: int = 0, device="cpu",
-                std: float = 0.02, bias_std: float = 0.02, optimizer_mode: str = "dat") -> Dict[str, torch.Tensor]:
+                std: float = 0.02, bias_std: float = 0.02, optimizer_mode: str = "dat",
+                num_labels: int = 100) -> Dict[str, torch.Tensor]:
     """BERT-style init (adapter.py:5-14: N(0, 0.02) weights, LayerNorm 1/0) -- biases get a small N(0, bias_std)
     instead of exact zeros so that every bias path of the kernels is exercised.  optimizer_mode "adapter": the single adapter
     per layer, with init_bert_weights' own zero biases."""
     g = torch.Generator(device=device)
     g.manual_seed(seed)
     out = {}
-    for k, shp in param_shapes(layers, tasks, optimizer_mode=optimizer_mode).items():
+    for k, shp in param_shapes(layers, tasks, num_labels=num_labels, optimizer_mode=optimizer_mode).items():
         is_ln = ("LayerNorm" in k) or ("layernorm" in k) or ("clf_norm0" in k)
         if optimizer_mode == "adapter" and ".adapter.adapter_" in k and k.endswith("bias"):
             out[k] = torch.zeros(shp, device=device)

@@ -554,6 +554,21 @@ int feddat_dat_loss_fwd_bwd_rows(const float* logits, const float* teacher, cons
                                  float* dlogits, float* scalars, int* nonfinite, hipStream_t stream);
 int feddat_bce_loss_fwd_bwd_rows(const float* logits, const float* target, int n, int B, int C, float* dlogits, float* scalars,
                                  int* nonfinite, hipStream_t stream);
+/* The DAT loss at ANY width -- additions within ABI 8 (the three one-launch forms above take C <= 128; the reference trains the
+ * same head at whatever num_labels the task says: src/configs/task_configs_fed.py lists `vqa` at 3129, and its loss is
+ * task_trainer.py:299-301, 506-516 at every width).  1 <= n <= B <= 4096, any C >= 1; n == B is the full batch.
+ *   dlogits[b, j] = 0.5 / n * ((sigmoid(x) - y) + T (p - q)) for rows [0, n), rows [n, B) are written as 0.0f;
+ *   scalars[0..2] = BCE_sum / n, KL_sum / n * T^2, and their half-sum; rows >= n of logits / teacher / target are never read;
+ *   *nonfinite (DEVICE int, may be NULL) is OR-ed with 1 when scalars[0] + scalars[1] is inf / NaN.
+ * Two launches: one workgroup of 256 threads per row (up to 4096 columns the row's operands stay in registers over the three
+ * passes, wider rows re-read them; no alignment is assumed of a row), which leaves the row's two terms in workspace[2 b],
+ * workspace[2 b + 1]; then one wave adds rows [0, n) (lane b % 64 in row order, then across the wave) and writes scalars and
+ * the flag.  Fixed-order sums, no float atomics: equal inputs give equal bits.  workspace: DEVICE floats,
+ * workspace_elems >= feddat_dat_loss_wide_workspace_elems(B) = 2 B. */
+long feddat_dat_loss_wide_workspace_elems(int B);
+int feddat_dat_loss_fwd_bwd_wide(const float* logits, const float* teacher, const float* target, int n, int B, int C, float temp,
+                                 float* dlogits, float* scalars, int* nonfinite, float* workspace, long workspace_elems,
+                                 hipStream_t stream);
 
 /* Gradients of per-column vectors over a long row dimension (optimizer_mode bias / norm: a linear layer's bias, a LayerNorm's
  * gamma and beta over R = B * S rows) -- additions within ABI 8 (csrc/vector_grad.hip).  Two stages, both with a summation order

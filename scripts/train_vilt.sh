@@ -4,6 +4,7 @@
 # one RCCL all-reduce.  NGPUS=1 runs all clients on one GPU exactly like the reference's sequential loop.
 # --pretrained_model_name must be a LOCAL HuggingFace directory (the reference's script: ./models/vilt-b32-mlm); a missing
 # path is an error -- drop the flag to run on random weights of the real architecture (synthetic benchmarks).
+# `--ordered_cl_tasks vqa` (appended): the reference's VQAv2 task, a federation with 3129-label heads (vilt_spec.TASK_NUM_LABELS).
 # The FedAvg baselines: append `--optimizer_mode adapter|bias|norm` (a later flag overrides the default below).
 NGPUS=${NGPUS:-1}
 export HSA_ENABLE_IPC_MODE_LEGACY=0
