@@ -377,6 +377,7 @@ class AlbefDatEngine(LocalUpdateEngine):
                 n = self.ad_numel
                 assert ms == tuple(range(ms[0], ms[0] + len(ms)))
                 ptrs = [self.ad[a].g[m * n:(m + 1) * n].data_ptr() for m in ms for a in (0, 1)]
+                assert all(p % 16 == 0 for p in ptrs)      # feddat_adapter_wgrad_reduce moves float4
                 self._segs_cache[key] = torch.tensor(ptrs, dtype=torch.int64, device=self.dev)
             ws = self.wpart_stride2
             # segments (adapter_0, adapter_1) = flags (B, A)
@@ -388,7 +389,9 @@ class AlbefDatEngine(LocalUpdateEngine):
         if key not in self._segs_cache:
             n, ws = self.ad_numel, self.wpart_stride
             contiguous = ms == tuple(range(ms[0], ms[0] + len(ms)))
-            ptrs = torch.tensor([self.ad[a].g[m * n:(m + 1) * n].data_ptr() for m in ms], dtype=torch.int64, device=self.dev)
+            ptrs = [self.ad[a].g[m * n:(m + 1) * n].data_ptr() for m in ms]
+            assert all(p % 16 == 0 for p in ptrs)      # feddat_adapter_wgrad_reduce moves float4
+            ptrs = torch.tensor(ptrs, dtype=torch.int64, device=self.dev)
             self._segs_cache[key] = (ptrs, contiguous)
         ptrs, contiguous = self._segs_cache[key]
         ws, flag = self.wpart_stride, self.ovf_flags[a:a + 1]

@@ -204,32 +204,67 @@ __global__ __launch_bounds__(256, 2) void wgrad_kernel(WgradLaunch L) {   // 2 b
 // grad layer layout: [wd (R x H) | bd (R) | wu (H x R) | bu (H)].  Returns whether a value it WROTE is inf / NaN (GradScaler's
 // inf check): in [R H, R H + R) su is the up problem's column sum of z, past it sd is the down problem's column sum of x --
 // by-products of the shared partial layout that are no gradient and are not checked.
-__device__ __forceinline__ bool wgrad_reduce_one(const float* __restrict__ partials, float* __restrict__ gl, int seg, int i) {
-    const float* Pd = partials + (size_t)(2 * seg) * NBLK * PSTRIDE;       // dW_down problem
-    const float* Pu = partials + (size_t)(2 * seg + 1) * NBLK * PSTRIDE;   // dW_up^T problem
-    float sd = 0.f, su = 0.f;
-#pragma unroll 4
-    for (int b = 0; b < NBLK; ++b) {
-        sd += Pd[(size_t)b * PSTRIDE + i];
-        su += Pu[(size_t)b * PSTRIDE + i];
-    }
-    if (i < R * H) {
-        gl[i] = sd;                                   // wd[r][c]
-        const int r = i / H, c = i - r * H;
-        gl[R * H + R + (size_t)c * R + r] = su;       // wu[c][r] (transpose of the computed [r][c])
-        return fd_nonfinite(sd) || fd_nonfinite(su);
-    }
-    if (i < R * H + R) {
-        gl[i] = sd;                                   // bd[r] = sum dz
-        return fd_nonfinite(sd);
-    }
-    gl[R * H + R + H * R + (i - R * H - R)] = su;     // bu[c] = s * sum dy
-    return fd_nonfinite(su);
+//
+// A block is RED_T threads, one float4 of output each, and all NBLK loads of a thread are in flight before its first add; every
+// element is the sequential fp32 sum ((0 + P_0) + P_1) + ... + P_{NBLK-1} of its partials.  blockIdx.x picks the block's piece:
+//   [0, RED_UT)           wu: all R units of RED_UC columns of the up problem (128-byte runs of each partial), turned through LDS
+//                         so that the tile leaves as ONE contiguous run of RED_UC * R floats of wu[c][r]
+//   [RED_UT, + RED_DB)    [wd | bd]: the down problem's partials and the gradient are both linear in the element index
+//   the last block        bu: the up problem's column sums
+// The by-products are not even read.  Needs 16-byte-aligned partials and gradients (every partial and every field of the
+// gradient layout is a whole number of float4 in).
+constexpr int RED_T = 384, RED_UC = 32;
+constexpr int RED_UT = H / RED_UC;                           // 24 wu tiles of R x RED_UC = RED_T float4
+constexpr int RED_DQ = (R * H + R) / 4;                      // float4 of [wd | bd]
+constexpr int RED_DB = (RED_DQ + RED_T - 1) / RED_T;
+constexpr int RED_BLOCKS = RED_UT + RED_DB + 1;
+constexpr int RED_LD = R + 4;                                // LDS row of one column's R units (+ 4: 2-way bank conflicts at most)
+static_assert(R * RED_UC == 4 * RED_T && H % RED_UC == 0 && (R * H) % 4 == 0 && R % 4 == 0 && H / 4 <= RED_T, "reduce tiling");
+
+__device__ __forceinline__ f32x4 wgrad_sum_partials(const float* __restrict__ p0) {
+    f32x4 p[NBLK];
+#pragma unroll
+    for (int b = 0; b < NBLK; ++b) p[b] = *reinterpret_cast<const f32x4*>(p0 + (size_t)b * PSTRIDE);
+    f32x4 s = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int b = 0; b < NBLK; ++b) s = s + p[b];
+    return s;
+}
+__device__ __forceinline__ bool fd_nonfinite4(const f32x4 v) {
+    return fd_nonfinite(v[0]) || fd_nonfinite(v[1]) || fd_nonfinite(v[2]) || fd_nonfinite(v[3]);
 }
 
-__global__ __launch_bounds__(256) void wgrad_reduce_kernel(WgradLaunch L) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < PSTRIDE) wgrad_reduce_one(L.partials, L.seg[blockIdx.y].grad, blockIdx.y, i);
+__device__ __forceinline__ bool wgrad_reduce_block(const float* __restrict__ partials, float* __restrict__ gl, int seg) {
+    __shared__ __attribute__((aligned(16))) float tile[RED_UC * RED_LD];
+    const float* Pd = partials + (size_t)(2 * seg) * NBLK * PSTRIDE;       // dW_down problem
+    const float* Pu = partials + (size_t)(2 * seg + 1) * NBLK * PSTRIDE;   // dW_up^T problem
+    const int blk = blockIdx.x, q = threadIdx.x;
+    if (blk < RED_UT) {                                                    // wu[c][r] (transpose of the computed [r][c])
+        const int c0 = blk * RED_UC, r = q / (RED_UC / 4), cq = q % (RED_UC / 4);
+        const f32x4 su = wgrad_sum_partials(Pu + (size_t)r * H + c0 + 4 * cq);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) tile[(4 * cq + e) * RED_LD + r] = su[e];
+        __syncthreads();
+        const int c = q / (R / 4), r4 = 4 * (q % (R / 4));
+        const f32x4 o = *reinterpret_cast<const f32x4*>(tile + c * RED_LD + r4);
+        *reinterpret_cast<f32x4*>(gl + R * H + R + (size_t)(c0 + c) * R + r4) = o;
+        return fd_nonfinite4(o);
+    }
+    if (blk < RED_UT + RED_DB) {                                           // wd[r][c], then bd[r] = sum dz
+        const int i = ((blk - RED_UT) * RED_T + q) * 4;
+        if (i >= R * H + R) return false;
+        const f32x4 sd = wgrad_sum_partials(Pd + i);
+        *reinterpret_cast<f32x4*>(gl + i) = sd;
+        return fd_nonfinite4(sd);
+    }
+    if (q >= H / 4) return false;
+    const f32x4 su = wgrad_sum_partials(Pu + R * H + R + 4 * q);           // bu[c] = s * sum dy
+    *reinterpret_cast<f32x4*>(gl + R * H + R + H * R + 4 * q) = su;
+    return fd_nonfinite4(su);
+}
+
+__global__ __launch_bounds__(RED_T) void wgrad_reduce_kernel(WgradLaunch L) {
+    wgrad_reduce_block(L.partials, L.seg[blockIdx.y].grad, blockIdx.y);
 }
 
 // the reductions of several launches (one per layer) in ONE: blockIdx.z = launch, its partials at + z * stride
@@ -240,11 +275,9 @@ struct WgradReduceBatch {
     int nseg;
     int* nonfinite;           // [nseg] or NULL: OR-ed with 1 when a segment's gradients hold an inf / NaN
 };
-__global__ __launch_bounds__(256) void wgrad_reduce_batched_kernel(WgradReduceBatch B) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    bool bad = false;
-    if (i < PSTRIDE)
-        bad = wgrad_reduce_one(B.partials + (size_t)blockIdx.z * B.stride, B.grads[blockIdx.z * B.nseg + blockIdx.y], blockIdx.y, i);
+__global__ __launch_bounds__(RED_T) void wgrad_reduce_batched_kernel(WgradReduceBatch B) {
+    const bool bad =
+        wgrad_reduce_block(B.partials + (size_t)blockIdx.z * B.stride, B.grads[blockIdx.z * B.nseg + blockIdx.y], blockIdx.y);
     if (B.nonfinite && __ballot(bad) != 0 && (threadIdx.x & 63) == 0) atomicOr(B.nonfinite + blockIdx.y, 1);
 }
 
@@ -261,11 +294,12 @@ static int wgrad_launch(const feddat_wgrad_seg* segs, int nseg, float* partials,
     L.partials = partials;
     for (int s = 0; s < nseg; ++s) {
         FD_CHECK_ARG(segs[s].x && segs[s].dy && segs[s].z && segs[s].dz && segs[s].grad && segs[s].rows > 0);
+        FD_CHECK_ARG(!reduce_now || (((uintptr_t)segs[s].grad | (uintptr_t)partials) & 15) == 0);      // the reduction moves float4
         L.seg[s] = segs[s];
     }
     if (nseg == 1) L.seg[1] = L.seg[0];
     hipLaunchKernelGGL(wgrad_kernel, dim3(NBLK, NCH, 2 * nseg), dim3(256), 0, stream, L);
-    if (reduce_now) hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((PSTRIDE + 255) / 256, nseg), dim3(256), 0, stream, L);
+    if (reduce_now) hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(RED_BLOCKS, nseg), dim3(RED_T), 0, stream, L);
     FD_LAUNCH_RET();
 }
 
@@ -283,7 +317,8 @@ extern "C" int feddat_adapter_wgrad_reduce(float* const* grads_dev, int n, int n
                                            long partials_stride, hipStream_t stream) {
     FD_CHECK_ARG(grads_dev && partials && n > 0 && n <= 65535 && nseg >= 1 && nseg <= 2);
     FD_CHECK_ARG(partials_stride >= (long)nseg * 2 * NBLK * PSTRIDE);
-    hipLaunchKernelGGL(wgrad_reduce_batched_kernel, dim3((PSTRIDE + 255) / 256, nseg, n), dim3(256), 0, stream,
+    FD_CHECK_ARG(((uintptr_t)partials & 15) == 0 && partials_stride % 4 == 0);      // float4 accesses (the gradients too)
+    hipLaunchKernelGGL(wgrad_reduce_batched_kernel, dim3(RED_BLOCKS, nseg, n), dim3(RED_T), 0, stream,
                        WgradReduceBatch{grads_dev, partials, partials_stride, nseg, nullptr});
     FD_LAUNCH_RET();
 }
@@ -292,7 +327,8 @@ extern "C" int feddat_adapter_wgrad_reduce_checked(float* const* grads_dev, int 
                                                    long partials_stride, int* nonfinite, hipStream_t stream) {
     FD_CHECK_ARG(grads_dev && partials && n > 0 && n <= 65535 && nseg >= 1 && nseg <= 2 && nonfinite);
     FD_CHECK_ARG(partials_stride >= (long)nseg * 2 * NBLK * PSTRIDE);
-    hipLaunchKernelGGL(wgrad_reduce_batched_kernel, dim3((PSTRIDE + 255) / 256, nseg, n), dim3(256), 0, stream,
+    FD_CHECK_ARG(((uintptr_t)partials & 15) == 0 && partials_stride % 4 == 0);      // float4 accesses (the gradients too)
+    hipLaunchKernelGGL(wgrad_reduce_batched_kernel, dim3(RED_BLOCKS, nseg, n), dim3(RED_T), 0, stream,
                        WgradReduceBatch{grads_dev, partials, partials_stride, nseg, nonfinite});
     FD_LAUNCH_RET();
 }

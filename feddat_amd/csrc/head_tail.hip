@@ -657,20 +657,55 @@ struct AdamwMulti {
     int warmup, total;
 };
 
+// the weight decays of elements i .. i + 3 from the segment table (off / wdv: in LDS, or in global memory for a table too long for it)
+__device__ __forceinline__ void adamw_quad_wd(const long* off, const float* wdv, const int nseg, const long i, float (&wd)[4]) {
+    int lo = 0, hi = nseg - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (off[mid] <= i) lo = mid; else hi = mid - 1;
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) wd[e] = wdv[lo];
+    if (lo + 1 < nseg && off[lo + 1] < i + 4) {
+        for (int e = 1; e < 4; ++e) {
+            int s2 = lo;
+            while (s2 + 1 < nseg && off[s2 + 1] <= i + e) ++s2;
+            wd[e] = wdv[s2];
+        }
+    }
+}
+
 // adamw_flat_kernel<4>'s arithmetic (loss_optim.hip; bit-identical per element) for up to three parameter groups in one
 // launch; a group reads its schedule index / Adam step count at (state[0] + d_sched, state[1] + d_adam).
+// The stream (g, p, m, v: 16 of the 28 bytes a parameter moves) is asked for FIRST: the flags, the counters and the segment table
+// are a chain of dependent reads that used to stand in front of it.  The loads are harmless on a skipped or restored block.
+// The block then takes its group's segment table into LDS once (every lane searched it in global memory: ~log2(nseg) dependent
+// round trips) and thread 0 evaluates the two bias corrections for the block -- the same powf calls on the same arguments.
+constexpr int ADAMW_SEG_LDS = 1024;      // a longer table is searched in global memory as before
 __global__ __launch_bounds__(256) void adamw_multi_kernel(const AdamwMulti a) {
+    __shared__ long s_off[ADAMW_SEG_LDS];
+    __shared__ float s_wd[ADAMW_SEG_LDS];
+    __shared__ float s_bc[2];
     int k = 0;
     while (k + 1 < a.ngroups && (int)blockIdx.x >= a.block_end[k]) ++k;
     const feddat_adamw_group& G = a.grp[k];
     const int blk = (int)blockIdx.x - (k ? a.block_end[k - 1] : 0);
     const long i = ((long)blk * 256 + threadIdx.x) * 4;
-    if (i >= G.n) return;
+    const bool live = i < G.n;
+    f32x4 gi = {0.f, 0.f, 0.f, 0.f}, pi = gi, mi = gi, vi = gi;
+    if (live) {
+        gi = *reinterpret_cast<const f32x4*>(G.g + i);
+        pi = *reinterpret_cast<const f32x4*>(G.p + i);
+        mi = *reinterpret_cast<const f32x4*>(G.m + i);
+        vi = *reinterpret_cast<const f32x4*>(G.v + i);
+    }
     // dynamic loss scale (ABI 8): restore / skip decisions are block-uniform device flags (head_tail.hip)
     if (G.bak_mode == 2 && G.restore_if && *G.restore_if) {
-        *reinterpret_cast<f32x4*>(G.p + i) = *reinterpret_cast<const f32x4*>(G.bak + i);
-        *reinterpret_cast<f32x4*>(G.m + i) = *reinterpret_cast<const f32x4*>(G.bak + G.n + i);
-        *reinterpret_cast<f32x4*>(G.v + i) = *reinterpret_cast<const f32x4*>(G.bak + 2 * G.n + i);
+        if (live) {
+            *reinterpret_cast<f32x4*>(G.p + i) = *reinterpret_cast<const f32x4*>(G.bak + i);
+            *reinterpret_cast<f32x4*>(G.m + i) = *reinterpret_cast<const f32x4*>(G.bak + G.n + i);
+            *reinterpret_cast<f32x4*>(G.v + i) = *reinterpret_cast<const f32x4*>(G.bak + 2 * G.n + i);
+        }
         return;
     }
     const bool skip = (G.skip_if[0] && *G.skip_if[0]) || (G.skip_if[1] && *G.skip_if[1]);
@@ -678,40 +713,41 @@ __global__ __launch_bounds__(256) void adamw_multi_kernel(const AdamwMulti a) {
     const int sched_t = G.state[0] + G.d_sched;
     const int t = G.state[1] + G.d_adam + 1;
     const float lr = a.base_lr * ht_poly_lambda(sched_t, a.warmup, a.total);
-    int lo = 0, hi = G.nseg - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (G.seg_off[mid] <= i) lo = mid; else hi = mid - 1;
-    }
-    float wd[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) wd[e] = G.seg_wd[lo];
-    if (lo + 1 < G.nseg && G.seg_off[lo + 1] < i + 4) {
-        for (int e = 1; e < 4; ++e) {
-            int s2 = lo;
-            while (s2 + 1 < G.nseg && G.seg_off[s2 + 1] <= i + e) ++s2;
-            wd[e] = G.seg_wd[s2];
+    const bool table_in_lds = G.nseg <= ADAMW_SEG_LDS;
+    if (table_in_lds)
+        for (int s = threadIdx.x; s < G.nseg; s += 256) {
+            s_off[s] = G.seg_off[s];
+            s_wd[s] = G.seg_wd[s];
         }
+    if (threadIdx.x == 0) {
+        s_bc[0] = 1.0f - powf(a.beta1, (float)t);
+        s_bc[1] = 1.0f - powf(a.beta2, (float)t);
     }
-    const float bc1 = 1.0f - powf(a.beta1, (float)t);
-    const float bc2 = 1.0f - powf(a.beta2, (float)t);
-    f32x4 gi = *reinterpret_cast<const f32x4*>(G.g + i);
-    f32x4 pi = *reinterpret_cast<const f32x4*>(G.p + i);
-    f32x4 mi = *reinterpret_cast<const f32x4*>(G.m + i);
-    f32x4 vi = *reinterpret_cast<const f32x4*>(G.v + i);
+    __syncthreads();
+    if (!live) return;
+    float wd[4];
+    if (table_in_lds) adamw_quad_wd(s_off, s_wd, G.nseg, i, wd);
+    else adamw_quad_wd(G.seg_off, G.seg_wd, G.nseg, i, wd);
+    const float bc1 = s_bc[0], bc2 = s_bc[1];
     if (G.bak_mode == 1) {
         *reinterpret_cast<f32x4*>(G.bak + i) = pi;
         *reinterpret_cast<f32x4*>(G.bak + G.n + i) = mi;
         *reinterpret_cast<f32x4*>(G.bak + 2 * G.n + i) = vi;
         if (skip) return;
     }
+    // adamw_flat_kernel's expressions (loss_optim.hip):
+    //     p *= 1 - lr wd;   m += (g - m)(1 - beta1);   v = v beta2 + (1 - beta2) g g;   p -= (lr / bc1)(m / (sqrt v / sqrt bc2 + eps))
+    // with the multiply-adds hipcc fused in this kernel spelled out.  Left to the compiler the fusions change with the code around
+    // the expressions (they did when the loads moved in front of the table search: half of the v updates came out unfused), and
+    // the trained weights with them.
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-        pi[e] = pi[e] * (1.0f - lr * wd[e]);
-        mi[e] = mi[e] + (gi[e] - mi[e]) * (1.0f - a.beta1);
-        vi[e] = vi[e] * a.beta2 + (1.0f - a.beta2) * gi[e] * gi[e];
+#pragma clang fp contract(off)
+        const float keep = __builtin_fmaf(-lr, wd[e], 1.0f);
+        mi[e] = __builtin_fmaf(gi[e] - mi[e], 1.0f - a.beta1, mi[e]);
+        vi[e] = __builtin_fmaf(vi[e], a.beta2, (1.0f - a.beta2) * gi[e] * gi[e]);
         const float denom = sqrtf(vi[e]) / sqrtf(bc2) + a.eps;
-        pi[e] -= (lr / bc1) * (mi[e] / denom);
+        pi[e] = __builtin_fmaf(pi[e], keep, -((lr / bc1) * (mi[e] / denom)));
     }
     *reinterpret_cast<f32x4*>(G.p + i) = pi;
     *reinterpret_cast<f32x4*>(G.m + i) = mi;

@@ -530,6 +530,7 @@ class ViltDatEngine(ViltBackbone):
         if key not in self._segs_cache:
             n = self.ad_layer_numel
             ptrs = [self.ad[a].g[i * n:(i + 1) * n].data_ptr() for i in range(self.nl) for a in ads]
+            assert all(p % 16 == 0 for p in ptrs)      # feddat_adapter_wgrad_reduce moves float4 (it cannot check a device table)
             self._segs_cache[key] = torch.tensor(ptrs, dtype=torch.int64, device=self.dev)
         # flags[a] for adapter a
         self._reduce_wgrads(self._segs_cache[key], self.nl, len(ads), self.wpart_all, self.wpart_stride, self.ovf_flags[ads[0]:])

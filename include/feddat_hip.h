@@ -342,7 +342,8 @@ int feddat_adapter_wgrad(const feddat_wgrad_seg* segs, int nseg, float* partials
  * token-split partial sums of ONE launch in `partials` (no reduction); _reduce folds the partials of n such launches --
  * launch l's at partials + l * partials_stride floats -- into their gradient buffers in one kernel (same fixed summation
  * order as feddat_adapter_wgrad: bit-identical results).  grads_dev: DEVICE array of n * nseg gradient pointers
- * ([launch][segment]), every launch with the same nseg. */
+ * ([launch][segment]), every launch with the same nseg.  The reduction moves 16 bytes per lane: partials, every gradient
+ * buffer and (in floats) partials_stride % 4 are 16-byte aligned, also for feddat_adapter_wgrad. */
 int feddat_adapter_wgrad_partial(const feddat_wgrad_seg* segs, int nseg, float* partials, long partials_elems, int H, int r,
                                  hipStream_t stream);
 int feddat_adapter_wgrad_reduce(float* const* grads_dev, int n, int nseg, const float* partials, long partials_stride,
