@@ -4,6 +4,9 @@
     model.activate_gating(); model.set_active_adapter('adapter_0')      # albef.py:139-171 fan-out over the 30 Adapter modules
     loss, logits = model(task_key, batch)        # batch['train'] = True : ALBEF.forward(train=True)  (albef.py:52-60)
     ids, probs   = model(task_key, batch)        # batch['train'] = False: rank_answer over batch['answer_list'] (albef.py:61-73)
+                                                 # any nq <= batch_size questions (a short last batch), any k <= len(answer_list),
+                                                 # entries of up to a_len - 1 tokens + the appended [SEP]: AlbefDatEngine.rank_answer
+                                                 # runs the candidates in slabs of the engine's n_answers
 
 Batches are the reference's (convert_batch_to_albef_input_dict, albef.py:275-286): {"images": [B,3,R,R] tensor, "questions":
 [str], "answers": [str], "weights": [n], "n": answers per question, "alpha", "train"} -- tokenised ONCE per batch by the device

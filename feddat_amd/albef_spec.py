@@ -104,3 +104,44 @@ def synthetic_batch(B: int, seed: int, image: int = 384, q_len: int = 25, a_len:
     out = {kk: v.to(device) for kk, v in batch.items()}
     out["k"] = k
     return out
+
+
+def synthetic_answer_list(M: int, a_len: int = 4, vocab: int = 30522, seed: int = 0):
+    """A stand-in for the task's tokenised answer list (albef.py:62-64): -> (ids [M, a_len], mask [M, a_len]) int64.  Entry i is
+    [CLS] t ... [SEP]; the first tokens t are distinct (rank_answer shortlists by the first token's probability, so two entries with
+    the same one would tie), and every third entry is one token shorter, [CLS] ... [SEP] [PAD] with mask 0 on the padding.
+    Deterministic in (M, a_len, vocab, seed)."""
+    lo, hi = 1000, min(30000, vocab)
+    if M < 1 or a_len < 3 or M > hi - lo:
+        raise ValueError(f"synthetic_answer_list: need 1 <= M <= {hi - lo} distinct first tokens and a_len >= 3, got M={M}, a_len={a_len}")
+    g = torch.Generator().manual_seed(seed)
+    ids = torch.randint(lo, hi, (M, a_len), generator=g)
+    ids[:, 1] = torch.randperm(hi - lo, generator=g)[:M] + lo
+    ids[:, 0], ids[:, -1] = 101, 102
+    mask = torch.ones(M, a_len, dtype=torch.long)
+    if a_len > 3:
+        ids[2::3, -2], ids[2::3, -1] = 102, 0
+        mask[2::3, -1] = 0
+    return ids, mask
+
+
+def synthetic_eval_loader(Q: int, batch_size: int, seed: int, answer_ids, answer_mask, k: int, image: int = 384, q_len: int = 25,
+                          vocab: int = 30522, device="cpu"):
+    """Q evaluation questions in batches of batch_size, the LAST ONE SHORT when Q is no multiple (the reference's eval loader keeps
+    it: vqa_dataset_crossvqa.py:580-603).  Each batch is what ALBEFContinualLearner.forward(train=False) takes -- image, question_ids /
+    question_mask, the answer list (answer_list_ids / answer_list_mask, shared by all batches), k -- plus gts: per question 1-3
+    indices into the answer list, the ground truth AlbefTaskTrainer.eval_one_loader scores against (task_trainer.py:188-196)."""
+    g = torch.Generator().manual_seed(seed)
+    M = answer_ids.shape[0]
+    answer_ids, answer_mask = answer_ids.to(device), answer_mask.to(device)
+    loader = []
+    for first in range(0, Q, batch_size):
+        n = min(batch_size, Q - first)
+        q = torch.randint(1000, min(30000, vocab), (n, q_len), generator=g)
+        q[:, 0], q[:, -1] = 101, 102
+        img = torch.randn(n, 3, image, image, generator=g)
+        gts = [torch.randperm(M, generator=g)[:min(M, 1 + int(torch.randint(0, 3, (1,), generator=g)))].tolist() for _ in range(n)]
+        loader.append({"image": img.to(device), "question_ids": q.to(device),
+                       "question_mask": torch.ones(n, q_len, dtype=torch.long, device=device), "answer_list_ids": answer_ids,
+                       "answer_list_mask": answer_mask, "k": k, "gts": gts})
+    return loader

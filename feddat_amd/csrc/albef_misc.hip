@@ -307,7 +307,132 @@ __global__ __launch_bounds__(256) void topk_rows_kernel(const float* __restrict_
     }
 }
 
+// rank_answer on the training frame: a batch of nq < B questions.  Sample j in [nq, B) of the image, the question ids and the
+// question mask becomes a copy of sample j mod nq (feddat_vilt_pad_batch's idea: finite activations and a non-empty key mask in
+// the samples nobody reads).  blockIdx.z = buffer, blockIdx.y = tail sample, blockIdx.x strides over the sample's bytes: uint4
+// where the sample's source and destination are 16-byte aligned (the image always is; a question row of Lq int64 is when
+// Lq is even), 8-byte words otherwise (every per-sample size is a multiple of 8: the launcher checks it).
+struct PadQuestions {
+    char* base[3];
+    long bytes[3];       // per sample
+    int nq;
+};
+__global__ __launch_bounds__(256) void pad_questions_kernel(PadQuestions a) {
+    const long bytes = a.bytes[blockIdx.z];
+    const int j = a.nq + blockIdx.y;
+    const char* src = a.base[blockIdx.z] + (long)(j % a.nq) * bytes;
+    char* dst = a.base[blockIdx.z] + (long)j * bytes;
+    const long tid = (long)blockIdx.x * 256 + threadIdx.x, nthr = (long)gridDim.x * 256;
+    long done = 0;
+    if (((((uintptr_t)src) | ((uintptr_t)dst)) & 15) == 0) {
+        const long nv = bytes / 16;
+        const uint4* s4 = reinterpret_cast<const uint4*>(src);
+        uint4* d4 = reinterpret_cast<uint4*>(dst);
+        for (long i = tid; i < nv; i += nthr) d4[i] = s4[i];
+        done = nv * 16;
+    }
+    const uint2* s2 = reinterpret_cast<const uint2*>(src + done);
+    uint2* d2 = reinterpret_cast<uint2*>(dst + done);
+    const long nw = (bytes - done) / 8;
+    for (long i = tid; i < nw; i += nthr) d2[i] = s2[i];
+}
+
+// rank_answer, pass 2 on a frame of N answers: slab s holds the candidates c = b k + j in [s N, min((s + 1) N, nq k)), row i of
+// the frame = candidate s N + i = entry topk_ids[c] of the answer list.  One thread per (row, position) of the [N, La] frame;
+// neighbouring threads write neighbouring int64 words (a row of La = 5 ids is 40 bytes, so rows are not 16-byte aligned and
+// each lane moves one 8-byte word).  Rows past the slab's last candidate (and a shortlist index outside the list) are dead:
+// the list's [CLS] alone and live at position 0, labels -100, row_w 0 -- what set_batch gives padded answers.
+struct SlabGather {
+    const long *topk, *list_ids, *list_mask;
+    long *ids, *mask, *labels;
+    uint8_t* mask8;
+    float* row_w;
+    int ncand, M, la, N, La, first;       // first = s N
+    long pad_id;
+};
+__global__ __launch_bounds__(256) void rank_slab_gather_kernel(SlabGather a) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= a.N * a.La) return;
+    const int i = e / a.La, t = e - i * a.La;
+    const int c = a.first + i;
+    long ans = c < a.ncand ? a.topk[c] : -1;
+    const bool live = ans >= 0 && ans < a.M;
+    if (!live) ans = 0;
+    const long* src = a.list_ids + ans * a.la;
+    long id = a.pad_id, m = 0;
+    if (live && t < a.la) {
+        id = src[t];
+        m = a.list_mask[ans * a.la + t];
+    } else if (!live && t == 0) {
+        id = src[0];
+        m = 1;
+    }
+    a.ids[e] = id;
+    a.mask[e] = m;
+    if (a.mask8) a.mask8[e] = (uint8_t)(m != 0);
+    if (t < a.La - 1) {       // the LM row that predicts position t + 1
+        const long next = (live && t + 1 < a.la) ? src[t + 1] : a.pad_id;
+        const int r = i * (a.La - 1) + t;
+        a.labels[r] = next == a.pad_id ? -100 : next;
+        a.row_w[r] = live ? 1.f : 0.f;
+    }
+}
+
+// rank_answer, pass 2: the sequence loss of candidate s N + i = the sum of the CE terms of its La - 1 LM rows, i.e. of
+// row_terms[2 r] (r = i (La - 1) + t) that feddat_lm_loss_fwd_bwd left behind `scalars + 4`, added in the order t = 0, 1, ...
+// One thread per candidate.
+__global__ __launch_bounds__(64) void rank_slab_loss_kernel(const float* __restrict__ row_terms, int La1, int live, int first,
+                                                            float* __restrict__ answer_loss) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= live) return;
+    const float* t = row_terms + (size_t)2 * i * La1;
+    float acc = 0.f;
+    for (int j = 0; j < La1; ++j) acc += t[2 * j];
+    answer_loss[first + i] = acc;
+}
+
 }  // namespace
+
+extern "C" int feddat_albef_pad_questions(float* image, long* question_ids, long* question_mask, int nq, int B, long image_elems,
+                                          int Lq, hipStream_t stream) {
+    FD_CHECK_ARG(image && question_ids && question_mask && B > 0 && B <= 65535 && nq >= 1 && nq <= B);
+    FD_CHECK_ARG(image_elems > 0 && image_elems % 4 == 0 && Lq > 0);
+    FD_CHECK_ARG(((uintptr_t)image & 15) == 0 && (((uintptr_t)question_ids | (uintptr_t)question_mask) & 7) == 0);
+    if (nq == B) return FEDDAT_OK;
+    PadQuestions a{};
+    a.base[0] = (char*)image, a.base[1] = (char*)question_ids, a.base[2] = (char*)question_mask;
+    a.bytes[0] = image_elems * 4, a.bytes[1] = a.bytes[2] = (long)Lq * 8;
+    a.nq = nq;
+    // grid.x is sized by the image (110 592 16-byte words per 384 x 384 sample, capped at 64 blocks); for the two question
+    // buffers all blocks but the first find nothing to do
+    const unsigned gx = (unsigned)min((a.bytes[0] / 16 + 255) / 256, 64L);
+    hipLaunchKernelGGL(pad_questions_kernel, dim3(gx, B - nq, 3), dim3(256), 0, stream, a);
+    FD_LAUNCH_RET();
+}
+
+extern "C" int feddat_rank_slab_gather(const long* topk_ids, const long* list_ids, const long* list_mask, long* answer_ids,
+                                       long* answer_mask, uint8_t* answer_mask8, long* labels, float* row_w, int nq, int k,
+                                       int M, int la, int B, int N, int La, int slab, long pad_id, hipStream_t stream) {
+    FD_CHECK_ARG(topk_ids && list_ids && list_mask && answer_ids && answer_mask && labels && row_w);
+    FD_CHECK_ARG(B > 0 && nq >= 1 && nq <= B && N >= B && M >= 1 && k >= 1 && k <= M && la >= 2 && la <= La);
+    FD_CHECK_ARG((long)N * La < (1L << 31) && (long)nq * k < (1L << 31));
+    FD_CHECK_ARG(slab >= 0 && (long)slab * N < (long)nq * k);
+    SlabGather a{topk_ids, list_ids, list_mask, answer_ids, answer_mask, labels, answer_mask8, row_w, nq * k, M, la, N, La,
+                 slab * N, pad_id};
+    hipLaunchKernelGGL(rank_slab_gather_kernel, dim3((N * La + 255) / 256), dim3(256), 0, stream, a);
+    FD_LAUNCH_RET();
+}
+
+extern "C" int feddat_rank_slab_loss(const float* scalars, float* answer_loss, int nq, int k, int B, int N, int La, int slab,
+                                     hipStream_t stream) {
+    FD_CHECK_ARG(scalars && answer_loss && B > 0 && nq >= 1 && nq <= B && N >= B && k >= 1 && La >= 2);
+    FD_CHECK_ARG((long)N * La < (1L << 31) && (long)nq * k < (1L << 31));
+    FD_CHECK_ARG(slab >= 0 && (long)slab * N < (long)nq * k);
+    const int first = slab * N, live = min(N, nq * k - first);
+    hipLaunchKernelGGL(rank_slab_loss_kernel, dim3((live + 63) / 64), dim3(64), 0, stream, scalars + 4, La - 1, live, first,
+                       answer_loss);
+    FD_LAUNCH_RET();
+}
 
 extern "C" int feddat_softmax_gather_rows(const float* logits, long row_stride, int rows, int V, const long* ids,
                                           long id_stride, int n, float* out, hipStream_t stream) {

@@ -185,6 +185,9 @@ _SIGS = {
     "feddat_vilt_pad_batch": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],
     "feddat_softmax_gather_rows": [vp, i64, i32, i32, vp, i64, i32, vp, vp],
     "feddat_topk_rows": [vp, i64, vp, i32, i32, i32, i32, vp, vp, vp],
+    "feddat_albef_pad_questions": [vp, vp, vp, i32, i32, i64, i32, vp],
+    "feddat_rank_slab_gather": [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i64, vp],
+    "feddat_rank_slab_loss": [vp, vp, i32, i32, i32, i32, i32, i32, vp],
     "feddat_gather_rows": [vp, vp, vp, vp, i32, i32, vp],
     "feddat_segment_sum_rows": [vp, vp, vp, i32, i32, i32, vp],
     "feddat_adamw_flat": [vp, vp, vp, vp, i64, vp, vp, i32, vp, f32, i32, i32, f32, f32, f32, vp],
@@ -1031,6 +1034,42 @@ def topk_rows(vals, k, *, minus=None, log_first=False, softmax=False):
     _chk(load().feddat_topk_rows(_p(vals), vals.stride(0), _p(minus), rows, n, k, (1 if log_first else 0) | (2 if softmax else 0),
                                  _p(ov), _p(oi), _stream()), "feddat_topk_rows")
     return ov, oi
+
+
+def albef_pad_questions(image, question_ids, question_mask, nq: int):
+    """feddat_albef_pad_questions on an ALBEF engine's static inputs (image fp32 [B, 3, R, R]; question_ids / question_mask int64
+    [B, Lq]): samples [nq, B) become copies of samples j mod nq."""
+    _dev(image, question_ids, question_mask)
+    B, Lq = question_ids.shape
+    assert image.dtype == torch.float32 and image.is_contiguous() and image.shape[0] == B
+    assert all(t.dtype == torch.int64 and t.is_contiguous() and tuple(t.shape) == (B, Lq) for t in (question_ids, question_mask))
+    _chk(load().feddat_albef_pad_questions(_p(image), _p(question_ids), _p(question_mask), int(nq), B, image[0].numel(), Lq,
+                                           _stream()), "feddat_albef_pad_questions")
+
+
+def rank_slab_gather(topk_ids, list_ids, list_mask, answer_ids, answer_mask, answer_mask8, labels, row_w, B: int, slab: int,
+                     pad_id: int):
+    """feddat_rank_slab_gather: slab `slab` of the shortlist topk_ids [nq, k] (device int64) -> the [N, La] answer frame, its
+    labels and per-row weights."""
+    _dev(topk_ids, list_ids, list_mask, answer_ids, answer_mask, answer_mask8, labels, row_w)
+    (nq, k), (M, la), (N, La) = topk_ids.shape, list_ids.shape, answer_ids.shape
+    assert all(t.dtype == torch.int64 and t.is_contiguous() for t in (topk_ids, list_ids, list_mask, answer_ids, answer_mask, labels))
+    assert tuple(list_mask.shape) == (M, la) and tuple(answer_mask.shape) == (N, La)
+    assert answer_mask8 is None or (answer_mask8.dtype == torch.uint8 and answer_mask8.is_contiguous() and tuple(answer_mask8.shape) == (N, La))
+    assert labels.numel() == N * (La - 1) and row_w.dtype == torch.float32 and row_w.is_contiguous() and row_w.numel() == N * (La - 1)
+    _chk(load().feddat_rank_slab_gather(_p(topk_ids), _p(list_ids), _p(list_mask), _p(answer_ids), _p(answer_mask), _p(answer_mask8),
+                                        _p(labels), _p(row_w), nq, k, M, la, int(B), N, La, int(slab), int(pad_id), _stream()),
+         "feddat_rank_slab_gather")
+
+
+def rank_slab_loss(scalars, answer_loss, nq: int, k: int, B: int, N: int, La: int, slab: int):
+    """feddat_rank_slab_loss: answer_loss[slab * N + i] = the sum of candidate i's La - 1 CE terms in `scalars` (what
+    lm_loss_fwd_bwd wrote for the slab's logits)."""
+    _dev(scalars, answer_loss)
+    assert scalars.dtype == torch.float32 and scalars.is_contiguous() and scalars.numel() >= 4 + 2 * N * (La - 1)
+    assert answer_loss.dtype == torch.float32 and answer_loss.is_contiguous() and answer_loss.numel() == nq * k
+    _chk(load().feddat_rank_slab_loss(_p(scalars), _p(answer_loss), int(nq), int(k), int(B), int(N), int(La), int(slab), _stream()),
+         "feddat_rank_slab_loss")
 
 
 def dropout(x, drop, *, resid=None, out_f32=None, out_bf16=None):

@@ -330,6 +330,14 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--synthetic_last_batch", type=int, default=0,
                    help="ViLT modes: samples in each client's LAST synthetic batch, 1 .. batch_size (a loader that does not drop "
                         "its short last batch, like the reference's: vqa_dataset_crossvqa.py:509-515); 0 = every batch full")
+    p.add_argument("--synthetic_answer_list", type=int, default=0,
+                   help="ALBEF: entries of a seeded synthetic answer list (albef_spec.synthetic_answer_list).  > 0 turns the periodic "
+                        "evaluation on (main.py:520): every fifth round and the last one each client ranks k = min(64, M) answers "
+                        "for its eval questions, three scores (gating, adapter_0, adapter_1).  0 = no list, no evaluation")
+    p.add_argument("--synthetic_eval_questions", type=int, default=None,
+                   help="ALBEF with --synthetic_answer_list: evaluation questions per client, in batches of min(val_batch_size, "
+                        "batch_size) with a short last one (drop_last=False: vqa_dataset_crossvqa.py:580-603).  Default "
+                        "batch_size + 1")
     p.add_argument("--image_size", type=int, default=384)
     p.add_argument("--num_layers", type=int, default=12)
     p.add_argument("--albef_dropout", type=float, default=0.1,
@@ -385,6 +393,12 @@ def main(argv=None):
         if not 1 <= args.synthetic_last_batch <= args.batch_size:
             raise L.FeddatHipError(f"--synthetic_last_batch must lie in 1 .. batch_size ({args.batch_size}), got "
                                    f"{args.synthetic_last_batch}")
+    if args.synthetic_answer_list < 0:
+        raise L.FeddatHipError(f"--synthetic_answer_list must be >= 0, got {args.synthetic_answer_list}")
+    if args.synthetic_answer_list and "albef" not in args.encoder_name:
+        raise L.FeddatHipError("--synthetic_answer_list is an ALBEF option (answer ranking); ViLT scores its answer head")
+    if args.synthetic_eval_questions is not None and args.synthetic_eval_questions < 1:
+        raise L.FeddatHipError(f"--synthetic_eval_questions must be >= 1, got {args.synthetic_eval_questions}")
     tasks = TASK_SETS.get(args.ordered_cl_tasks, args.ordered_cl_tasks.split(","))
     # the head width of the federation, from the reference's task table (vqa: 3129 labels); ALBEF has no answer head
     num_labels = federation_num_labels(tasks) if "albef" not in args.encoder_name else None
@@ -471,6 +485,19 @@ def main(argv=None):
     last = args.synthetic_last_batch or None
     data = {t: [make_batch(args.seed + 1000 * ti + s, ti, last if s == steps_of[t] - 1 else None) for s in range(steps_of[t])]
             for ti, t in enumerate(tasks) if t in my_tasks}
+    # what a client is evaluated on: ViLT, two of its training batches; ALBEF with an answer list, its own eval questions
+    eval_data = {t: data[t][:2] for t in my_tasks}
+    albef_eval = albef and args.synthetic_answer_list > 0
+    if albef_eval:
+        M, vocab = args.synthetic_answer_list, dims.get("vocab", 30522)
+        a_ids, a_mask = albef_spec.synthetic_answer_list(M, eng.La, vocab, args.seed)
+        Q = args.synthetic_eval_questions if args.synthetic_eval_questions is not None else args.batch_size + 1
+        eval_data = {t: albef_spec.synthetic_eval_loader(Q, min(args.val_batch_size, args.batch_size), args.seed + 500000 + ti, a_ids,
+                                                         a_mask, min(64, M), image=args.image_size, q_len=eng.Lq, vocab=vocab,
+                                                         device=dev)      # k: task_trainer.py:172
+                     for ti, t in enumerate(tasks) if t in my_tasks}
+    # {round: {client: scores}} of the periodic evaluation, and what it ran on: kept on the returned model
+    model.eval_scores, model.eval_data, model.personal_params = {}, eval_data, personal_params
     server_flat = eng.comm_flat().clone()
     acc = torch.zeros_like(server_flat)
     # the exchange: one C-ABI collective per round (main.py:510 get_average_net -> feddat_fedavg_allreduce); the local
@@ -510,7 +537,7 @@ def main(argv=None):
             eng.comm_written()
             model.load_state_dict(personal_params[task_key])        # main.py:473-478
             model.adapter_requires_grad = dict(server_flags)
-            trainer = Trainer(args, task_key, data[task_key], data[task_key][:2], log)
+            trainer = Trainer(args, task_key, data[task_key], eval_data[task_key], log)
             trainer.dropout_epoch = comm_round * len(tasks) + tasks.index(task_key)     # fresh dropout masks per round and client
             trainer.defer_finite_check = world > 1
             trainer.train(model, comm_round)
@@ -545,17 +572,18 @@ def main(argv=None):
                     flags_after.update({0: False, 1: True})         # the eval below leaves the server in this state
                 checkpoint.save_federation(args.output_dir, {n: sd[n] for n in comm_names}, {}, comm_round,
                                            server_flags=flags_after)
-        if (comm_round % 5 == 0 or comm_round == args.comm_rounds - 1) and not albef:   # main.py:520 (ALBEF: the synthetic
-            for task_key in my_tasks:                                                     # stand-in has no answer list)
+        if (comm_round % 5 == 0 or comm_round == args.comm_rounds - 1) and (not albef or albef_eval):   # main.py:520
+            for task_key in my_tasks:        # (ALBEF: only with --synthetic_answer_list, see below)
                 eng.comm_flat().copy_(server_flat)
                 model.load_state_dict(personal_params[task_key])
                 model.after_load()
                 model.adapter_requires_grad = dict(server_flags)
-                scores = TaskTrainer(args, task_key, data[task_key], data[task_key][:2], log).eval(model)
+                scores = Trainer(args, task_key, data[task_key], eval_data[task_key], log).eval(model)
                 server_flags = dict(model.adapter_requires_grad)
+                model.eval_scores.setdefault(comm_round, {})[task_key] = scores
                 log.info("round %d %s test score server = %s", comm_round, task_key, scores)
         elif comm_round % 5 == 0 or comm_round == args.comm_rounds - 1:
-            # ALBEF: the synthetic stand-in has no answer list to rank, so the periodic evaluation is skipped -- but its
+            # ALBEF without an answer list: there is nothing to rank, so the periodic evaluation is skipped -- but its
             # side effect on the SERVER model is not: TaskTrainer.eval ends in set_active_adapter('adapter_1')
             # (task_trainer.py:236-244 -> adapter.py:79-85), so every client optimizer built from the next round on
             # (create_optimizer filters on requires_grad, task_trainer.py:477-504) no longer holds adapter_0.

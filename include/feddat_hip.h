@@ -650,6 +650,30 @@ int feddat_softmax_gather_rows(const float* logits, long row_stride, int rows, i
                                float* out, hipStream_t stream);
 int feddat_topk_rows(const float* vals, long ld, const float* minus, int rows, int n, int k, int flags, float* out_vals,
                      long* out_idx, hipStream_t stream);
+/* Additions within ABI 8: rank_answer on the TRAINING frame (B questions, N >= B answers of La tokens), for nq <= B questions,
+ * any k <= M and answer lists of la <= La tokens.  The nq k candidates (candidate c = b k + j = entry topk_ids[b, j] of the list) go
+ * through the decoder in slabs of N: slab s holds c in [s N, min((s + 1) N, nq k)).  Every call checks its arguments and returns
+ * FEDDAT_EINVAL (nothing written) on a NULL pointer, nq < 1, nq > B, N < B, k < 1, k > M, la < 2, la > La or a slab with no candidate.
+ * feddat_albef_pad_questions: samples [nq, B) of image (fp32 [B, image_elems], image_elems % 4 == 0, 16-byte aligned),
+ *   question_ids and question_mask (int64 [B, Lq], 8-byte aligned) become copies of samples j mod nq -- no attention row of the
+ *   unused samples is empty.  One launch, 16-byte copies (8-byte ones for question rows that are not 16-byte aligned); nq == B
+ *   launches nothing.
+ * feddat_rank_slab_gather: from the shortlist topk_ids (DEVICE int64 [nq, k]: no read-back between the two decoder passes) and
+ *   the answer list (list_ids / list_mask int64 [M, la]) the frame's inputs for slab `slab`: answer_ids / answer_mask int64 [N, La]
+ *   (pad_id / 0 behind la), answer_mask8 (uint8 [N, La], may be NULL), labels int64 [N (La - 1)] = next-token ids, -100 at padding,
+ *   at positions >= la - 1 and in rows past the slab's last candidate, row_w fp32 [N (La - 1)] = 1 on a candidate's rows, 0
+ *   elsewhere.  Rows past the last candidate hold the list's first token alone, live at position 0 (what the engine's set_batch
+ *   gives padded answers); so does a row whose shortlist index lies outside [0, M).
+ * feddat_rank_slab_loss: answer_loss[slab N + i] = sum_t scalars[4 + 2 (i (La - 1) + t)], t = 0 .. La - 2 in that order, for the
+ *   slab's candidates i -- the per-row CE terms feddat_lm_loss_fwd_bwd wrote into `scalars` (4 + 2 N (La - 1) floats) for the
+ *   slab's logits; answer_loss: fp32 [nq k]. */
+int feddat_albef_pad_questions(float* image, long* question_ids, long* question_mask, int nq, int B, long image_elems, int Lq,
+                               hipStream_t stream);
+int feddat_rank_slab_gather(const long* topk_ids, const long* list_ids, const long* list_mask, long* answer_ids,
+                            long* answer_mask, uint8_t* answer_mask8, long* labels, float* row_w, int nq, int k, int M, int la,
+                            int B, int N, int La, int slab, long pad_id, hipStream_t stream);
+int feddat_rank_slab_loss(const float* scalars, float* answer_loss, int nq, int k, int B, int N, int La, int slab,
+                          hipStream_t stream);
 
 
 /* ---------------------------------------------------------------------------------------------
