@@ -238,6 +238,121 @@ __global__ __launch_bounds__(256) void image_assemble_masked_kernel(const float*
     *reinterpret_cast<f32x4*>(h + ((size_t)b * S + Lt + t) * H + c * 4) = o;
 }
 
+// ---- patch slots: the image half of the sequence holds max_patches slots per sample instead of the frame's gh x gw cells.
+// Slot j < vh * vw of a sample holds cell (j / vw, j % vw) of its valid rectangle (row-major: HF visual_embed's valid_row_idx
+// order with max_image_length = -1); slots behind that are empty.
+
+// sample's valid rectangle from its patch mask [gh, gw], as image_assemble_masked_kernel counts it: threads 0..gh-1 look at
+// patch column 0, threads 64..64+gw-1 at patch row 0 (gh, gw <= 64).  Every thread of the block calls this.
+__device__ __forceinline__ void fd_valid_rect(const long* __restrict__ pm, int gh, int gw, int* cnt, int& vh, int& vw) {
+    if (threadIdx.x < 2) cnt[threadIdx.x] = 0;
+    __syncthreads();
+    const int t_ = threadIdx.x;
+    if (t_ < gh && pm[(size_t)t_ * gw] != 0) atomicAdd(&cnt[0], 1);
+    if (t_ >= 64 && t_ - 64 < gw && pm[t_ - 64] != 0) atomicAdd(&cnt[1], 1);
+    __syncthreads();
+    vh = cnt[0];
+    vw = cnt[1];
+}
+
+// pixels [n,C,Hi,Wi] fp32 -> patches [B*mp, C*P*P] 16-bit: block (j, b) writes slot j of sample b from sample b % n's pixels
+// (a short batch's replicas), one thread = 4 consecutive px of one patch row (im2col_kernel's conversion); empty slots are zero
+__global__ __launch_bounds__(256) void im2col_slots_kernel(const float* __restrict__ px, const long* __restrict__ pmask,
+                                                           bf16* __restrict__ out, int n, int C, int Hi, int Wi, int P,
+                                                           int mp) {
+    const int gw = Wi / P, gh = Hi / P;
+    const int j = blockIdx.x, b = blockIdx.y;
+    __shared__ int cnt[2];
+    int vh, vw;
+    fd_valid_rect(pmask + (size_t)b * gh * gw, gh, gw, cnt, vh, vw);
+    const int nq = C * P * P / 4;
+    bf16* o = out + ((size_t)b * mp + j) * ((size_t)C * P * P);
+    if (j >= vh * vw) {
+        const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+        for (int q = threadIdx.x; q < nq; q += 256) *reinterpret_cast<bf16x4*>(o + q * 4) = cvt4(z);
+        return;
+    }
+    const int cy = j / vw, cx = j - cy * vw;
+    const float* src = px + (size_t)(b % n) * C * Hi * Wi + (size_t)cy * P * Wi + (size_t)cx * P;
+    for (int q = threadIdx.x; q < nq; q += 256) {
+        const int col = q * 4;
+        const int ix = col % P, iy = (col / P) % P, c = col / (P * P);
+        const f32x4 v = *reinterpret_cast<const f32x4*>(src + ((size_t)c * Hi + iy) * Wi + ix);
+        *reinterpret_cast<bf16x4*>(o + col) = cvt4(v);
+    }
+}
+
+// image_assemble_masked_kernel on slots: row Lt + 1 + j of sample b = proj[b * mp + j] + (the g x g grid resized to the
+// sample's vh x vw rectangle, at the slot's cell: the expressions of the grid kernel, bit-identical values) + modality[1];
+// an empty slot adds no position value.  Block (0, b) writes the key mask (slot j: the patch mask at its cell; empty: 0) and
+// raises *overflow when the sample has more valid patches than slots (it never clears it).
+__global__ __launch_bounds__(256) void image_assemble_slots_kernel(const float* __restrict__ proj,
+                                                                   const float* __restrict__ cls,
+                                                                   const float* __restrict__ pos0,
+                                                                   const float* __restrict__ grid,
+                                                                   const long* __restrict__ pmask,
+                                                                   const long* __restrict__ amask,
+                                                                   const float* __restrict__ mod1, float* __restrict__ h,
+                                                                   uint8_t* __restrict__ key_mask, int* __restrict__ overflow,
+                                                                   int B, int Lt, int gh, int gw, int mp, int g, int S, int H,
+                                                                   int nrep) {
+    const int nc = H >> 2;
+    const int b = blockIdx.y;
+    const long* pm = pmask + (size_t)b * gh * gw;
+    __shared__ int cnt[2];
+    int vh, vw;
+    fd_valid_rect(pm, gh, gw, cnt, vh, vw);
+    const int count = vh * vw;
+    if (blockIdx.x == 0) {
+        if (threadIdx.x == 0 && overflow && count > mp) *overflow = 1;
+        if (key_mask) {
+            for (int t = threadIdx.x; t < S; t += 256) {
+                uint8_t v = 1;
+                if (t < Lt) {
+                    if (amask) v = amask[(size_t)b * Lt + t] != 0;
+                } else if (t > Lt) {
+                    const int j = t - Lt - 1;
+                    v = 0;
+                    if (j < count) {
+                        const int y = j / vw, x = j - y * vw;
+                        v = pm[(size_t)y * gw + x] != 0;
+                    }
+                }
+                for (int r = 0; r < nrep; ++r) key_mask[(size_t)(b + r * B) * S + t] = v;
+            }
+        }
+    }
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long)(mp + 1) * nc) return;
+    const int c = (int)(i % nc);
+    const int t = (int)(i / nc);
+    const f32x4 m4 = *reinterpret_cast<const f32x4*>(mod1 + c * 4);
+    f32x4 o;
+    if (t == 0) {
+        o = (*reinterpret_cast<const f32x4*>(cls + c * 4) + *reinterpret_cast<const f32x4*>(pos0 + c * 4)) + m4;
+    } else {
+        const int p = t - 1;
+        f32x4 v = {0.f, 0.f, 0.f, 0.f};
+        if (p < count) {
+            const int y = p / vw, x = p - y * vw;
+            const float sy = vh > 1 ? ((float)(g - 1) / (float)(vh - 1)) * (float)y : 0.f;
+            const float sx = vw > 1 ? ((float)(g - 1) / (float)(vw - 1)) * (float)x : 0.f;
+            const int y0 = min((int)sy, g - 1), x0 = min((int)sx, g - 1);
+            const int y1 = min(y0 + 1, g - 1), x1 = min(x0 + 1, g - 1);
+            const float ly = sy - (float)y0, lx = sx - (float)x0;
+            const f32x4 v00 = *reinterpret_cast<const f32x4*>(grid + ((size_t)y0 * g + x0) * H + c * 4);
+            const f32x4 v01 = *reinterpret_cast<const f32x4*>(grid + ((size_t)y0 * g + x1) * H + c * 4);
+            const f32x4 v10 = *reinterpret_cast<const f32x4*>(grid + ((size_t)y1 * g + x0) * H + c * 4);
+            const f32x4 v11 = *reinterpret_cast<const f32x4*>(grid + ((size_t)y1 * g + x1) * H + c * 4);
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                v[e] = fd_bilerp(v00[e], v01[e], v10[e], v11[e], ly, lx);
+        }
+        o = (*reinterpret_cast<const f32x4*>(proj + ((size_t)b * mp + p) * H + c * 4) + v) + m4;
+    }
+    *reinterpret_cast<f32x4*>(h + ((size_t)b * S + Lt + t) * H + c * 4) = o;
+}
+
 // attention key mask of the [text | CLS | patches] sequence, written nrep times (rows b + rep * B)
 __global__ __launch_bounds__(256) void key_mask_kernel(const long* __restrict__ amask, const long* __restrict__ pmask,
                                                        uint8_t* __restrict__ out, int B, int Lt, int Hi, int Wi, int P,
@@ -361,6 +476,32 @@ extern "C" int feddat_image_embed_assemble_masked(const float* proj, const float
     const long per = (long)(np + 1) * (H / 4);
     hipLaunchKernelGGL(image_assemble_masked_kernel, dim3((unsigned)((per + 255) / 256), B), dim3(256), 0, stream, proj, cls,
                        pos0, pos_grid, patch_mask, attention_mask, modality1, h, key_mask, B, Lt, gh, gw, g, S, H, nrep);
+    FD_LAUNCH_RET();
+}
+
+extern "C" int feddat_im2col_patches_slots(const float* pixels, const long* patch_mask, void* patches_bf16, int n, int B,
+                                           int C, int Hi, int Wi, int P, int max_patches, hipStream_t stream) {
+    FD_CHECK_ARG(pixels && patch_mask && patches_bf16 && B > 0 && B <= 65535 && C > 0 && Hi > 0 && Wi > 0 && P > 0);
+    FD_CHECK_ARG(Hi % P == 0 && Wi % P == 0 && P % 4 == 0 && Hi / P <= 64 && Wi / P <= 64);
+    FD_CHECK_ARG(n >= 1 && n <= B && max_patches >= 1 && max_patches <= (Hi / P) * (Wi / P));
+    hipLaunchKernelGGL(im2col_slots_kernel, dim3(max_patches, B), dim3(256), 0, stream, pixels, patch_mask,
+                       (bf16*)patches_bf16, n, C, Hi, Wi, P, max_patches);
+    FD_LAUNCH_RET();
+}
+
+extern "C" int feddat_image_embed_assemble_slots(const float* proj, const float* cls, const float* pos0,
+                                                 const float* pos_grid, const long* patch_mask,
+                                                 const long* attention_mask, const float* modality1, float* h,
+                                                 uint8_t* key_mask, int* overflow, int B, int Lt, int gh, int gw,
+                                                 int max_patches, int g, int H, int nrep, hipStream_t stream) {
+    FD_CHECK_ARG(proj && cls && pos0 && pos_grid && patch_mask && modality1 && h && B > 0 && B <= 65535 && Lt >= 0);
+    FD_CHECK_ARG(gh > 0 && gw > 0 && gh <= 64 && gw <= 64 && g > 0 && H > 0 && H % 4 == 0 && nrep >= 1);
+    FD_CHECK_ARG(max_patches >= 1 && max_patches <= gh * gw);
+    const int S = Lt + 1 + max_patches;
+    const long per = (long)(max_patches + 1) * (H / 4);
+    hipLaunchKernelGGL(image_assemble_slots_kernel, dim3((unsigned)((per + 255) / 256), B), dim3(256), 0, stream, proj, cls,
+                       pos0, pos_grid, patch_mask, attention_mask, modality1, h, key_mask, overflow, B, Lt, gh, gw, max_patches,
+                       g, S, H, nrep);
     FD_LAUNCH_RET();
 }
 

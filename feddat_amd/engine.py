@@ -41,7 +41,7 @@ class ViltDatEngine(ViltBackbone):
                  weight_decay: float = 1e-2, adam_eps: float = 1e-8, wgrad_splits: int = 16, fp8: bool = False,
                  fp8_ffn_chain: bool = True, gelu_codes: bool = True, operands: Optional[str] = None,
                  loss_scale: Optional[float] = None, fp8_mx_dqkv: bool = True, dynamic_loss_scale: Optional[bool] = None,
-                 scale_growth_interval: int = 2000):
+                 scale_growth_interval: int = 2000, max_patches: Optional[int] = None):
         """operands: "f16" (the default) or "bf16" (the default with fp8=True, configs[4]).  "f16": every 16-bit MFMA operand of the step -- frozen weights and their transposes, LayerNorm outputs,
         qkv, probabilities, ctx, gelu(u), the adapters' operand copies, and every gradient operand of the dX products and of
         the attention backward -- is IEEE half instead of bf16 (libfeddat_hip_f16.so: v_mfma_f32_16x16x32_f16, the same MFMA
@@ -68,7 +68,11 @@ class ViltDatEngine(ViltBackbone):
         (FEDDAT_EPI_GELU / _MUL_DGELU instead of _GELU_G8 / _MUL_G8; middle layers issued op by op).  25 % more bytes through
         the two heaviest epilogues (+0.14 ms/step at configs[1]); at B = 32 it takes the worst adapter element after an 80-step
         round from 1.31e-3 to 1.00e-3 and the worst update-norm error from 2.9 % to 1.6 % -- for callers
-        that trade 2 % of throughput for that."""
+        that trade 2 % of throughput for that.
+        max_patches: patch slots instead of the grid frame (vilt_backbone.ViltBackbone); 16-bit operands only."""
+        if fp8 and max_patches is not None:
+            raise L.FeddatHipError("fp8=True takes the grid frame only (max_patches=None): configs[4] is a B = 64 configuration "
+                                   "with sequence limits of its own")
         operands = operands or ("bf16" if fp8 else "f16")
         if fp8 and operands != "bf16":
             raise L.FeddatHipError("fp8=True (configs[4]) pairs the e4m3 products with bf16 operands")
@@ -77,7 +81,7 @@ class ViltDatEngine(ViltBackbone):
         # of the eight frozen products per layer, and half the bytes of the backward's largest write
         self.fp8_mx_dqkv = bool(fp8) and bool(fp8_mx_dqkv)
         super().__init__(params, tasks, device, batch, res, text_len, layers, num_labels, lr, weight_decay, adam_eps, gelu_codes,
-                         operands, loss_scale, dynamic_loss_scale, scale_growth_interval)
+                         operands, loss_scale, dynamic_loss_scale, scale_growth_interval, max_patches)
         self._init_dat(params, wgrad_splits, fp8, fp8_ffn_chain, gelu_codes)
 
     @_bound

@@ -196,6 +196,8 @@ _SIGS = {
     "feddat_im2col_patches": [vp, vp, i32, i32, i32, i32, i32, vp],
     "feddat_image_embed_assemble": [vp, vp, vp, vp, i64, vp, vp, i32, i32, i32, i32, i32, vp],
     "feddat_image_embed_assemble_masked": [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp],
+    "feddat_im2col_patches_slots": [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp],
+    "feddat_image_embed_assemble_slots": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp],
     "feddat_pos_embed_resize_masked": [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],
     "feddat_vilt_key_mask": [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],
     "feddat_vilt_image_workspace_bytes": [vp, vp, vp, vp, i32],
@@ -1141,6 +1143,28 @@ def image_embed_assemble_masked(proj, cls, pos0, pos_grid, patch_mask, attention
 def im2col_patches(pixels, patches, B, Cc, Hi, Wi, P):
     _dev(pixels, patches)
     _chk(load().feddat_im2col_patches(_p(pixels), _p(patches), B, Cc, Hi, Wi, P, _stream()), "feddat_im2col_patches")
+
+
+def im2col_patches_slots(pixels, patch_mask, patches, n, B, Cc, Hi, Wi, P, max_patches):
+    """Patch slots: pixels fp32 [n, Cc, Hi, Wi] -> patches 16-bit [B * max_patches, Cc P P], slot j of sample b = cell
+    (j / vw, j % vw) of its valid rectangle (patch_mask: int64 [B, Hi/P, Wi/P]), read from sample b mod n; empty slots zero."""
+    _dev(pixels, patch_mask, patches)
+    if patch_mask.dtype != torch.int64 or pixels.dtype != torch.float32:
+        raise FeddatHipError("im2col_patches_slots takes fp32 pixels and an int64 patch mask")
+    _chk(load().feddat_im2col_patches_slots(_p(pixels), _p(patch_mask), _p(patches), n, B, Cc, Hi, Wi, P, max_patches,
+                                            _stream()), "feddat_im2col_patches_slots")
+
+
+def image_embed_assemble_slots(proj, cls, pos0, pos_grid, patch_mask, attention_mask, mod1, h, key_mask, overflow, B, Lt, gh, gw,
+                               max_patches, g, H, nrep=1):
+    """image_embed_assemble_masked on patch slots (proj: [B * max_patches, H]; h: [B, Lt + 1 + max_patches, H]); overflow:
+    int32 [1], set to 1 when a sample has more valid patches than slots."""
+    _dev(proj, h, patch_mask)
+    if patch_mask.dtype != torch.int64 or (overflow is not None and overflow.dtype != torch.int32):
+        raise FeddatHipError("image_embed_assemble_slots takes an int64 patch mask and an int32 overflow flag")
+    _chk(load().feddat_image_embed_assemble_slots(_p(proj), _p(cls), _p(pos0), _p(pos_grid), _p(patch_mask), _p(attention_mask),
+                                                  _p(mod1), _p(h), _p(key_mask), _p(overflow), B, Lt, gh, gw, max_patches, g, H,
+                                                  nrep, _stream()), "feddat_image_embed_assemble_slots")
 
 
 def image_embed_assemble(proj, cls, pos0, pos_img, mod1, h, B, Lt, npatch, S, H, pos_batch_stride=0):

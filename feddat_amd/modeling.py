@@ -196,9 +196,12 @@ class ViltContinualLearner:
     BERT_LOCAL_PATH = "./models/bert-base-uncased"       # vilt.py:47
 
     def __init__(self, ordered_cl_tasks: List[str], params: Dict[str, torch.Tensor], device, batch_size: int,
-                 image_size: int = 384, num_layers: int = 12, lr: float = 1e-4, vocab=None, operands: str = None,
-                 optimizer_mode: str = "dat", num_labels: int = 100):
-        """num_labels: width of every task head (task_configs_fed.py: 100 for the CLOVE / domain tasks, 3129 for vqa; one engine
+                 image_size=384, num_layers: int = 12, lr: float = 1e-4, vocab=None, operands: str = None,
+                 optimizer_mode: str = "dat", num_labels: int = 100, max_patches: Optional[int] = None):
+        """image_size: the engine's static pixel frame, an int (square) or (height, width).
+        max_patches: patch slots per sample instead of one sequence position per cell of the frame (ViltBackbone): with
+        image_size=(640, 640), max_patches=240 one engine takes every image the ViLT size rule yields, portrait and landscape.
+        num_labels: width of every task head (task_configs_fed.py: 100 for the CLOVE / domain tasks, 3129 for vqa; one engine
         has one width).
         operands: 16-bit MFMA operand format of the engine, "f16" (default; the reference's mixed_precision: fp16,
         accelerate_config.yaml:8) or "bf16" (engine.ViltDatEngine).
@@ -221,7 +224,8 @@ class ViltContinualLearner:
         else:
             raise L.FeddatHipError(f"optimizer_mode must be one of {MODES}, got {optimizer_mode!r}")
         self.engine = Engine(params, self.ordered_cl_tasks, self.device, batch=batch_size, res=image_size, layers=num_layers,
-                             lr=lr, operands=operands, num_labels=num_labels)
+                             lr=lr, operands=operands, num_labels=num_labels,
+                             **({} if max_patches is None else {"max_patches": max_patches}))
         self.num_labels = int(num_labels)
         self.max_text_length = self.engine.Lt               # vilt.py:50: config.max_position_embeddings = 40
         self._vocab = vocab
@@ -300,6 +304,7 @@ class ViltContinualLearner:
         if self._image_processor is None:
             from .image_processing import ViltImageProcessor
             # every batch is padded to the engine's static frame; patches outside an image's valid rectangle are masked keys
+            # (grid frame) or stay out of the sequence (patch slots)
             self._image_processor = ViltImageProcessor(self.device, pad_to=self.engine.res)
         return self._image_processor
 
@@ -313,6 +318,16 @@ class ViltContinualLearner:
         arrs = [np.asarray(im.convert("RGB")) if hasattr(im, "convert") else im for im in images]
         if len(arrs) != len(texts):
             raise L.FeddatHipError(f"{len(arrs)} images but {len(texts)} texts")
+        eng = self.engine
+        if eng.max_patches is not None:      # the slot budget, from the sizes alone (before any image is resized)
+            from .image_processing import resize_output_size
+            for i, a in enumerate(arrs):
+                shp = a.shape if hasattr(a, "shape") else None
+                if shp is not None and len(shp) == 3:
+                    oh, ow = resize_output_size(int(shp[0]), int(shp[1]))
+                    if (oh // eng.P) * (ow // eng.P) > eng.max_patches:
+                        raise L.FeddatHipError(f"image {i} ({shp[0]}x{shp[1]}) resizes to {oh}x{ow}: {(oh // eng.P) * (ow // eng.P)} "
+                                               f"patches, the engine was built with max_patches = {eng.max_patches}")
         enc = dict(self.image_processor(arrs))
         tok = self.tokenizer(list(texts), padding="max_length", truncation=True, max_length=self.max_text_length)
         enc.update(input_ids=tok["input_ids"], attention_mask=tok["attention_mask"], token_type_ids=tok["token_type_ids"])
@@ -330,13 +345,15 @@ class ViltContinualLearner:
 
 
 def create_vilt_continual_learner_model(params: Dict[str, torch.Tensor], ordered_cl_tasks: List[str], device,
-                                        batch_size: int, image_size: int = 384, num_layers: int = 12,
+                                        batch_size: int, image_size=384, num_layers: int = 12,
                                         lr: float = 1e-4, vocab=None, operands: str = None,
-                                        optimizer_mode: str = "dat", num_labels: int = 100) -> ViltContinualLearner:
+                                        optimizer_mode: str = "dat", num_labels: int = 100,
+                                        max_patches: Optional[int] = None) -> ViltContinualLearner:
     """vilt.py:421-452 (the pretrained checkpoint is passed in as a tensor dict: feddat_amd.weights.load_vilt_pretrained
     reads it from a local HF directory; there is no hub access here)."""
     return ViltContinualLearner(ordered_cl_tasks, params, device, batch_size, image_size, num_layers, lr, vocab=vocab,
-                                operands=operands, optimizer_mode=optimizer_mode, num_labels=num_labels)
+                                operands=operands, optimizer_mode=optimizer_mode, num_labels=num_labels,
+                                max_patches=max_patches)
 
 
 def convert_batch_to_vilt_input_dict(batch: Dict):

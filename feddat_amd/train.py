@@ -339,6 +339,16 @@ def build_parser() -> argparse.ArgumentParser:
                         "batch_size) with a short last one (drop_last=False: vqa_dataset_crossvqa.py:580-603).  Default "
                         "batch_size + 1")
     p.add_argument("--image_size", type=int, default=384)
+    p.add_argument("--image_frame", type=str, default=None,
+                   help="ViLT: H,W of the engine's pixel frame (multiples of 32) instead of the square --image_size frame, e.g. "
+                        "640,640 for a frame that holds portrait and landscape images")
+    p.add_argument("--max_image_patches", type=int, default=None,
+                   help="ViLT: patch slots per sample (ViltBackbone max_patches): each sample's valid patches are compacted into "
+                        "this many sequence positions instead of one position per cell of the frame; 240 covers every image of "
+                        "the ViLT size rule")
+    p.add_argument("--synthetic_orientations", action="store_true",
+                   help="ViLT: every synthetic sample draws its valid rectangle from a seeded list of landscape, portrait and "
+                        "square sizes inside the frame (vilt_spec.synthetic_mixed_batch), zero-padded with its pixel_mask")
     p.add_argument("--num_layers", type=int, default=12)
     p.add_argument("--albef_dropout", type=float, default=0.1,
                    help="hidden / attention-probability dropout of the ALBEF BERT towers under train_step (the reference's "
@@ -393,6 +403,27 @@ def main(argv=None):
         if not 1 <= args.synthetic_last_batch <= args.batch_size:
             raise L.FeddatHipError(f"--synthetic_last_batch must lie in 1 .. batch_size ({args.batch_size}), got "
                                    f"{args.synthetic_last_batch}")
+    frame = args.image_size
+    if args.image_frame is not None or args.max_image_patches is not None or args.synthetic_orientations:
+        if "albef" in args.encoder_name:
+            raise L.FeddatHipError("--image_frame, --max_image_patches and --synthetic_orientations are ViLT options: the ALBEF "
+                                   "engine takes one square image size")
+        if args.image_frame is not None:
+            try:
+                frame = tuple(int(x) for x in args.image_frame.split(","))
+            except ValueError:
+                frame = ()
+            if len(frame) != 2 or any(x < 32 or x % 32 for x in frame):
+                raise L.FeddatHipError(f"--image_frame takes H,W in multiples of 32, got {args.image_frame!r}")
+        if args.max_image_patches is not None:
+            fh, fw = (frame, frame) if isinstance(frame, int) else frame
+            cells, text_len = (fh // 32) * (fw // 32), 40
+            if not 1 <= args.max_image_patches <= cells:
+                raise L.FeddatHipError(f"--max_image_patches must lie in 1 .. {cells} (the cells of the {fh}x{fw} frame), got "
+                                       f"{args.max_image_patches}")
+            if text_len + 1 + args.max_image_patches > 320:
+                raise L.FeddatHipError(f"--max_image_patches {args.max_image_patches} makes sequences of "
+                                       f"{text_len + 1 + args.max_image_patches} tokens; the attention kernels take at most 320")
     if args.synthetic_answer_list < 0:
         raise L.FeddatHipError(f"--synthetic_answer_list must be >= 0, got {args.synthetic_answer_list}")
     if args.synthetic_answer_list and "albef" not in args.encoder_name:
@@ -462,10 +493,11 @@ def main(argv=None):
             log.info("loaded ViLT weights from %s", pretrained)
         else:                # no --pretrained_model_name: random weights of the real architecture (synthetic benchmarks)
             params = vilt_spec.random_init(args.num_layers, tasks, seed=args.seed, optimizer_mode=mode, num_labels=num_labels)
-        model = create_vilt_continual_learner_model(params, tasks, dev, args.batch_size, args.image_size,
+        model = create_vilt_continual_learner_model(params, tasks, dev, args.batch_size, frame,
                                                     args.num_layers, args.lr,
                                                     operands={"fp16": "f16", "bf16": "bf16"}[args.mixed_precision],
-                                                    optimizer_mode=mode, num_labels=num_labels)
+                                                    optimizer_mode=mode, num_labels=num_labels,
+                                                    max_patches=args.max_image_patches)
         Trainer = TaskTrainer
     eng = model.engine
     # personal parameters per client (main.py:440-450): head + adapter_0 + adapter_2 (dat) / head (adapter, bias, norm)
@@ -479,6 +511,12 @@ def main(argv=None):
                                               device=dev)
         prior = vilt_spec.client_label_prior(ti, num_labels, alpha=args.synthetic_label_alpha) \
             if args.synthetic_label_alpha > 0 else None
+        if args.synthetic_orientations:
+            return vilt_spec.synthetic_mixed_batch(n or args.batch_size, frame, seed, device=dev, num_labels=num_labels,
+                                                   label_prior=prior)
+        if not isinstance(frame, int):      # --image_frame without orientations: full images of the frame's size
+            return vilt_spec.synthetic_mixed_batch(n or args.batch_size, frame, seed, device=dev, num_labels=num_labels,
+                                                   label_prior=prior, sizes=[frame])
         return vilt_spec.synthetic_batch(n or args.batch_size, args.image_size, seed, device=dev, num_labels=num_labels,
                                          label_prior=prior)
     # --synthetic_last_batch N: the last batch of every client holds N samples (len(dataset) % batch_size != 0)

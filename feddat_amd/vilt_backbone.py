@@ -21,6 +21,8 @@ from . import lib as L
 from .local_update import FlatGroup, LocalUpdateEngine, _bound
 
 ENC = "vilt_encoder.vilt."
+# longest sequence the attention kernels take (csrc/attention.hip, csrc/attention_cls.hip)
+MAX_SEQ = 320
 HEAD_TENSORS = ("clf_fc0.weight", "clf_fc0.bias", "clf_norm0.weight", "clf_norm0.bias", "clf_fc1.weight",
                 "clf_fc1.bias")
 
@@ -35,12 +37,18 @@ class ViltBackbone(LocalUpdateEngine):
                  text_len: int = 40, layers: int = 12, num_labels: int = 100, lr: float = 1e-4,
                  weight_decay: float = 1e-2, adam_eps: float = 1e-8, gelu_codes: bool = True, operands: Optional[str] = None,
                  loss_scale: Optional[float] = None, dynamic_loss_scale: Optional[bool] = None,
-                 scale_growth_interval: int = 2000):
+                 scale_growth_interval: int = 2000, max_patches: Optional[int] = None):
         """operands ("f16", the default, or "bf16"), loss_scale, dynamic_loss_scale, scale_growth_interval and gelu_codes: see
-        engine.ViltDatEngine."""
+        engine.ViltDatEngine.
+        max_patches (None: the grid frame, every cell of the res frame is a sequence position): the image half of the sequence
+        holds max_patches PATCH SLOTS per sample, S = text_len + 1 + max_patches.  Each sample's valid patches (pixel_mask) are
+        compacted into its slots in row-major order, as HF visual_embed does with max_image_length = -1, so a frame that holds
+        portrait and landscape images (res up to 640 x 640) runs at the longest image's patch count (240).  A sample with more
+        valid patches than slots raises FeddatHipError: in set_batch for a host pixel_mask, at the end-of-update check
+        (assert_finite) for a device-resident one."""
         self._init_loss_scale(operands or "f16", loss_scale, dynamic_loss_scale, scale_growth_interval)
         self._init_backbone(params, tasks, device, batch, res, text_len, layers, num_labels, lr, weight_decay, adam_eps,
-                            gelu_codes)
+                            gelu_codes, max_patches)
 
     def _param(self, params, name):
         return params[name].to(self.dev, torch.float32).contiguous()
@@ -53,7 +61,7 @@ class ViltBackbone(LocalUpdateEngine):
 
     @_bound
     def _init_backbone(self, params, tasks, device, batch, res, text_len, layers, num_labels, lr, weight_decay, adam_eps,
-                       gelu_codes):
+                       gelu_codes, max_patches=None):
         L.load()
         self.dev = torch.device(device)
         self.tasks = list(tasks)
@@ -63,6 +71,19 @@ class ViltBackbone(LocalUpdateEngine):
         self.P = 32
         self.gh, self.gw = self.res[0] // self.P, self.res[1] // self.P
         self.np = self.gh * self.gw
+        # patch slots: self.np is the slot count (the patch matrix, the projection, the activations and the key mask shrink
+        # with it); None: one sequence position per grid cell
+        self.max_patches = None if max_patches is None else int(max_patches)
+        if self.max_patches is not None:
+            if not 1 <= self.max_patches <= self.gh * self.gw:
+                raise L.FeddatHipError(f"max_patches must lie in 1 .. {self.gh * self.gw} (the {self.gh} x {self.gw} cells of "
+                                       f"the {self.res[0]} x {self.res[1]} frame), got {max_patches}")
+            if text_len + 1 + self.max_patches > MAX_SEQ:
+                raise L.FeddatHipError(f"max_patches = {self.max_patches} makes sequences of {text_len + 1 + self.max_patches} "
+                                       f"tokens; the attention kernels take at most {MAX_SEQ}")
+            if max(self.gh, self.gw) > 64:
+                raise L.FeddatHipError("a patch-slot frame holds at most 64 x 64 cells")
+            self.np = self.max_patches
         self.S = text_len + 1 + self.np
         self.R = batch * self.S
         self.lr, self.wd, self.eps = lr, weight_decay, adam_eps
@@ -97,7 +118,8 @@ class ViltBackbone(LocalUpdateEngine):
         # per-sample position grids: the 12 x 12 table resized to each sample's valid patch rectangle (pixel_mask)
         self.pos_grid = pos[1:].contiguous()
         self.g0 = int(round(math.sqrt(pos.shape[0] - 1)))
-        self.pos_img = torch.empty(batch, self.np, H, device=dev)
+        if self.max_patches is None:
+            self.pos_img = torch.empty(batch, self.np, H, device=dev)
         self.w_patch = bf16_of(P(e + "patch_embeddings.projection.weight").reshape(H, 3 * self.P * self.P))
         self.layers: List[dict] = []
         for i in range(layers):
@@ -142,6 +164,12 @@ class ViltBackbone(LocalUpdateEngine):
         # inside the step (no host sync, valid for every batch under one captured graph); rows [B, 2B) repeat [0, B)
         self.key_mask2 = torch.ones(self.NPASS * B, self.S, dtype=torch.uint8, device=dev)
         self.patches = b16(B * self.np, 3 * self.P * self.P)
+        if self.max_patches is not None:
+            # raised by the slot kernel inside the step when a sample has more valid patches than slots (device-resident masks:
+            # nobody reads them on the host); read and cleared by assert_finite
+            self.slot_overflow = torch.zeros(1, dtype=torch.int32, device=dev)
+            # what feddat_vilt_pad_batch moves in the patch matrix' place: the slot gather reads a short batch's replicas itself
+            self._pad_stub = torch.zeros(B * self.gh * self.gw, 2, dtype=self.op_dtype, device=dev)
         self.proj = f32(B * self.np, H)
         self.h0 = f32(R, H)
         self.x16 = b16(R2, H)          # LN output (GEMM operand), transient
@@ -217,11 +245,60 @@ class ViltBackbone(LocalUpdateEngine):
         # followed by the same read inside the graph (stream-ordered with the replay that follows)
         if not px.is_cuda:
             px = px.to(self.dev, non_blocking=True)
+        if self.max_patches is not None:
+            self._set_batch_slots(batch, px, n)
+            return
         L.im2col_patches(px.to(torch.float32).contiguous(), self.patches, n, 3, self.res[0], self.res[1], self.P)
         self._stage_small_inputs(batch, n)
         if n < self.B:
             L.vilt_pad_batch(self.patches, self.inp, n, self.B)
         self.n_valid = n
+
+    def _set_batch_slots(self, batch, px, n: int):
+        """set_batch in a patch-slot frame: the masks first (the gather needs every sample's valid rectangle, the replicas'
+        too), then only the slot patches leave the pixels.  A host pixel_mask is checked against the slot budget here; a
+        device-resident one by the step's own kernel (self.slot_overflow)."""
+        pm = batch.get("pixel_mask")
+        if pm is not None and not pm.is_cuda:
+            from .vilt_spec import patch_slot_plan
+            _, counts, over = patch_slot_plan(pm[:, ::self.P, ::self.P], self.max_patches)
+            if bool(over.any()):
+                b = int(over.nonzero()[0])
+                raise L.FeddatHipError(f"sample {b} has {int(counts[b])} valid patches; the engine was built with max_patches = "
+                                       f"{self.max_patches} slots per sample")
+        self._stage_small_inputs(batch, n)
+        if n < self.B:
+            L.vilt_pad_batch(self._pad_stub, self.inp, n, self.B)
+        L.im2col_patches_slots(px.to(torch.float32).contiguous(), self.inp["patch_mask"], self.patches, n, self.B, 3, self.res[0],
+                               self.res[1], self.P, self.max_patches)
+        self.n_valid = n
+
+    def check_patch_slots(self):
+        """Raise if a batch since the last check held a sample with more valid patches than slots (one 4-byte read-back; the
+        flag is cleared, so training can go on with in-budget batches).  No-op in the grid frame."""
+        if self.max_patches is not None and int(self.slot_overflow.item()) != 0:
+            self.slot_overflow.zero_()
+            raise L.FeddatHipError(f"a sample had more valid patches than the engine's max_patches = {self.max_patches} slots: its "
+                                   "patches behind the budget were dropped from the sequence -- build the engine with more slots "
+                                   "(the ViLT size rule yields at most 240 patches)")
+
+    def _extra_step_state(self) -> List[torch.Tensor]:
+        """The slot-budget flag is raised inside the step: capturing (a warm-up and a capture run on whatever is staged) puts it
+        back like the rest of the step's state."""
+        return super()._extra_step_state() + ([self.slot_overflow] if self.max_patches is not None else [])
+
+    def assert_finite(self):
+        self.check_patch_slots()
+        super().assert_finite()
+
+    def nonfinite_groups(self) -> List[str]:
+        """LocalUpdateEngine.nonfinite_groups; a sample over the slot budget is reported here too (and the flag cleared), so
+        that the ranks of train.main agree on it before the FedAvg collective like on a non-finite group."""
+        bad = super().nonfinite_groups()
+        if self.max_patches is not None and int(self.slot_overflow.item()) != 0:
+            self.slot_overflow.zero_()
+            bad.append(f"patch slots (a sample had more valid patches than max_patches = {self.max_patches})")
+        return bad
 
     def _stage_small_inputs(self, batch, n: int):
         """input_ids, token_type_ids, attention_mask, target_scores and pixel_mask of n samples -> samples [0, n) of self.inp."""
@@ -265,6 +342,11 @@ class ViltBackbone(LocalUpdateEngine):
         # (self.patches was filled by set_batch: im2col of the caller's pixel_values)
         L.gemm_bf16_nt(self.patches, self.w_patch, L.EPI_F32, bias=e["patch_embeddings.projection.bias"],
                        out_f32=self.proj)
+        if self.max_patches is not None:      # patch slots: key mask + position value at each slot's cell + assembly + budget check
+            L.image_embed_assemble_slots(self.proj, self.cls, self.pos0, self.pos_grid, self.inp["patch_mask"],
+                                         self.inp["attention_mask"], self.mod1, self.h0, self.key_mask2, self.slot_overflow, B,
+                                         Lt, self.gh, self.gw, self.max_patches, self.g0, H, nrep=self.NPASS)
+            return
         if self.fused_tail:      # key mask + per-sample position grid + assembly in one launch (bit-identical)
             L.image_embed_assemble_masked(self.proj, self.cls, self.pos0, self.pos_grid, self.inp["patch_mask"],
                                           self.inp["attention_mask"], self.mod1, self.h0, self.key_mask2, B, Lt, self.gh,

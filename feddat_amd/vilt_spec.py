@@ -136,3 +136,88 @@ def synthetic_batch(B: int, res: int, seed: int, device="cpu", text_len: int = 4
              "attention_mask": torch.ones(B, text_len, dtype=torch.long),
              "token_type_ids": torch.zeros(B, text_len, dtype=torch.long), "target_scores": target}
     return {k: v.to(device) for k, v in batch.items()}
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# mixed frames: portrait, landscape and square images in one pixel frame, and the patch-slot layout of their sequences
+# ----------------------------------------------------------------------------------------------------------------------
+def pad_to_valid(batch: Dict[str, torch.Tensor], valid_hw: Sequence[Tuple[int, int]], text_lens: Sequence[int] = None):
+    """What the HF ViLT processor yields for images of different sizes in one frame: sample b keeps the top-left
+    valid_hw[b] = (h, w) pixels (multiples of the patch size), the rest is zero with pixel_mask = 0; with text_lens the
+    questions are padded ([PAD] = 0, attention_mask = 0) behind text_lens[b] tokens.  Returns a new batch."""
+    out = {k: v.clone() for k, v in batch.items()}
+    for i, (h, w) in enumerate(valid_hw):
+        out["pixel_mask"][i] = 0
+        out["pixel_mask"][i, :h, :w] = 1
+        out["pixel_values"][i] *= out["pixel_mask"][i][None].to(out["pixel_values"].dtype)
+    if text_lens is not None:
+        for i, n in enumerate(text_lens):
+            out["attention_mask"][i, n:] = 0
+            out["input_ids"][i, n:] = 0
+    return out
+
+
+def extend_frame(batch: Dict[str, torch.Tensor], frame: Tuple[int, int]):
+    """The same batch in a larger pixel frame: pixel_values and pixel_mask zero-extended to frame = (H, W)."""
+    out = dict(batch)
+    px, pm = batch["pixel_values"], batch["pixel_mask"]
+    n, _, h, w = px.shape
+    if frame[0] < h or frame[1] < w:
+        raise ValueError(f"frame {frame} is smaller than the batch's {h}x{w}")
+    out["pixel_values"] = px.new_zeros(n, 3, frame[0], frame[1])
+    out["pixel_values"][:, :, :h, :w] = px
+    out["pixel_mask"] = pm.new_zeros(n, frame[0], frame[1])
+    out["pixel_mask"][:, :h, :w] = pm
+    return out
+
+
+def orientation_sizes(frame: Tuple[int, int], patch: int = 32):
+    """The valid rectangles --synthetic_orientations draws from, inside frame = (H, W): the ViLT size rule's landscape (shorter
+    edge 0.6 of the longer), portrait and square, each as large as the frame allows, and a small landscape; multiples of the
+    patch size."""
+    H, W = frame
+
+    def fit(h, w):
+        return max(patch, min(H, h) // patch * patch), max(patch, min(W, w) // patch * patch)
+    long_ = max(H, W)
+    short = int(long_ * 0.6)
+    sizes = [fit(short, long_), fit(long_, short), fit(min(H, W) * 3 // 4, min(H, W) * 3 // 4), fit(short // 2, long_ * 3 // 4)]
+    return sizes
+
+
+def synthetic_mixed_batch(B: int, frame, seed: int, device="cpu", text_len: int = 40, num_labels: int = 100,
+                          label_prior: torch.Tensor = None, sizes: Sequence[Tuple[int, int]] = None):
+    """synthetic_batch in a frame = (H, W) (an int: square) whose samples draw their valid rectangle from `sizes` (default:
+    orientation_sizes(frame)) with a generator seeded by `seed`: zero-padded pixels and the pixel_mask that says so."""
+    frame = (frame, frame) if isinstance(frame, int) else tuple(frame)
+    sizes = list(sizes) if sizes is not None else orientation_sizes(frame)
+    side = max(frame)
+    b = synthetic_batch(B, side, seed, "cpu", text_len, num_labels, label_prior)
+    b["pixel_values"] = b["pixel_values"][:, :, :frame[0], :frame[1]].contiguous()
+    b["pixel_mask"] = b["pixel_mask"][:, :frame[0], :frame[1]].contiguous()
+    g = torch.Generator(device="cpu")
+    g.manual_seed(seed + 0x5EED)
+    pick = torch.randint(0, len(sizes), (B,), generator=g).tolist()
+    b = pad_to_valid(b, [sizes[i] for i in pick])
+    return {k: v.to(device) for k, v in b.items()}
+
+
+def patch_slot_plan(patch_mask: torch.Tensor, max_patches: int):
+    """The patch-slot layout (include/feddat_hip.h, "PATCH SLOTS") restated on the host.  patch_mask: [B, gh, gw], the pixel
+    mask at the patch origins.  Sample b's valid rectangle is vh x vw = the valid patch rows of patch column 0 times the valid
+    patch columns of patch row 0; slot j < min(vh * vw, max_patches) holds grid cell (j / vw, j % vw), as the flat index
+    (j / vw) * gw + j % vw; the slots behind are empty (-1).
+    Returns (cells int64 [B, max_patches], counts int64 [B] = vh * vw, overflow bool [B] = counts > max_patches)."""
+    pm = torch.as_tensor(patch_mask).cpu() != 0
+    B, gh, gw = pm.shape
+    if not 1 <= max_patches <= gh * gw:
+        raise ValueError(f"max_patches must lie in 1 .. {gh * gw}, got {max_patches}")
+    vh, vw = pm[:, :, 0].sum(1), pm[:, 0, :].sum(1)
+    counts = (vh * vw).to(torch.int64)
+    cells = torch.full((B, max_patches), -1, dtype=torch.int64)
+    for b in range(B):
+        n, w = min(int(counts[b]), max_patches), int(vw[b])
+        if n:
+            j = torch.arange(n)
+            cells[b, :n] = (j // w) * gw + j % w
+    return cells, counts, counts > max_patches

@@ -713,6 +713,28 @@ int feddat_image_embed_assemble_masked(const float* proj, const float* cls, cons
                                        const long* patch_mask, const long* attention_mask, const float* modality1, float* h,
                                        uint8_t* key_mask, int B, int Lt, int gh, int gw, int g, int H, int nrep,
                                        hipStream_t stream);
+/* Additions within ABI 8: PATCH SLOTS.  The image half of the sequence holds max_patches slots per sample instead of the
+ * frame's gh x gw grid cells (S = Lt + 1 + max_patches), which is what HF visual_embed does with max_image_length = -1: a frame
+ * that holds portrait and landscape images keeps the sequence at the longest image's patch count.  Sample b's valid rectangle
+ * is vh x vw (feddat_pos_embed_resize_masked's definition on patch_mask = pixel_mask at the patch origins, int64 [B, gh, gw]);
+ * slot j < vh * vw holds grid cell (j / vw, j % vw), slots behind that are empty.  A sample with more valid patches than slots
+ * keeps its first max_patches cells; nothing is written outside the slot range.
+ *
+ * feddat_im2col_patches_slots: pixels fp32 [n, C, Hi, Wi] -> patches 16-bit [B * max_patches, C*P*P], only the slot patches
+ * (rows bit-equal to feddat_im2col_patches' at the mapped cells), empty slots zero.  1 <= n <= B: sample b reads the pixels of
+ * sample b mod n (the replicas of a short batch); patch_mask holds all B samples. */
+int feddat_im2col_patches_slots(const float* pixels, const long* patch_mask, void* patches_bf16, int n, int B, int C, int Hi,
+                                int Wi, int P, int max_patches, hipStream_t stream);
+/* feddat_image_embed_assemble_masked on slots, one launch: h[b, Lt, :] = cls + pos[0] + modality[1];
+ * h[b, Lt+1+j, :] = proj[b*max_patches + j] + (pos_grid resized to vh x vw, at slot j's cell) + modality[1], the position value
+ * bit-identical with the one the grid kernel adds at that cell; an empty slot adds none (a finite row that depends on nothing
+ * but proj).  key_mask (uint8 [nrep * B, S], optional): text keys from attention_mask (NULL = all valid), CLS valid, slot j =
+ * patch_mask at its cell, empty slots 0.  overflow (int32, optional): set to 1 when a sample has more valid patches than
+ * slots, never cleared here. */
+int feddat_image_embed_assemble_slots(const float* proj, const float* cls, const float* pos0, const float* pos_grid,
+                                      const long* patch_mask, const long* attention_mask, const float* modality1, float* h,
+                                      uint8_t* key_mask, int* overflow, int B, int Lt, int gh, int gw, int max_patches, int g,
+                                      int H, int nrep, hipStream_t stream);
 /* bilinear(align_corners=True) resize of the [g,g,H] position grid to [gh,gw,H] (HF visual_embed) */
 int feddat_pos_embed_resize(const float* pos_grid, float* out, int g, int gh, int gw, int H, hipStream_t stream);
 /* Padded images (HF ViltEmbeddings.visual_embed, transformers modeling_vilt.py, called from vilt.py:127): pixel_mask is
