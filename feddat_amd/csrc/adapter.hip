@@ -293,7 +293,8 @@ __global__ __launch_bounds__(256, 2) void adapter_bwd_kernel(const float* __rest
 }
 
 // =====================================================================================================================
-// Weight-stationary persistent forms (the ones the entry points launch for every shape).
+// Weight-stationary persistent forms, four waves per block (launched for the fp8 copy of dx and under debug flag
+// FD_DEBUG_ADAPTER_4W; every other launch takes the two-wave-group forms further down, which compute the same bits).
 //
 // What bounded the one-tile-per-block kernels above (r02, PMC): 740 blocks in a single generation, each a serial chain
 // load -> ~1 us of compute fed by 216-288 KB of weight fragments through L1/L2 -> store, with HBM idle during the compute
@@ -887,7 +888,579 @@ __global__ __launch_bounds__(256, 1) void adapter_bwd_ws_kernel(const float* __r
     else ws_bwd_body<1, Q8>(dy, dx, dx16, z_out, dz_out, sg, t0, tstep, ntiles, ws_smem, z_saved, FD_ABL(L.dbg), dx8, dx8_scale);
 }
 
-// host: blocks per segment, proportional to the tiles (at least one block per non-empty segment, one block per CU in all)
+// =====================================================================================================================
+// Two wave groups per block: the forms the entry points launch (debug flag FD_DEBUG_ADAPTER_4W selects the four-wave
+// kernels above instead; the results are bit-identical).
+//
+// What bounded the four-wave kernels (tools/adapter_ablate.py): with one wave per SIMD the compute phase of a tile
+// is ONE dependent chain per SIMD -- LDS fragment reads, MFMA latencies, two block exchanges -- and nothing else can issue
+// under it; a second wave per SIMD could not hold the gated segment's 288 weight dwords in its 256 registers.  Here a block
+// has 8 waves, two per SIMD: group = wave >> 2, quarter w4 = wave & 3 (the four-wave kernels' `wave`), and the weights are
+// SPLIT, not replicated:
+//   * gated segment: group a keeps adapter a's quarter (144 dwords) and runs a's down-type product, K-split sum and
+//     up-type product.  The two terms meet in the tile buffer, so no further LDS is needed: behind a block barrier every
+//     wave has taken its fragments, group 0 adds s0 (y0 + b0) to the residual in place, and behind a second barrier group 1
+//     adds s1 (y1 + b1), which it held in registers: o = x + s0 (y0 + b0) + s1 (y1 + b1) in the four-wave order (a = 0, then
+//     a = 1);
+//   * single-adapter segment: the down-type product is split by r-tile (group 0: r-tiles 0 and 1, group 1: r-tile 2; the
+//     K-split stays 4-way over the same quarters), the up-type product by column tile (group g: tiles 6 g .. 6 g + 5 of the
+//     quarter); every wave sums all three K-split tiles;
+//   * the LayerNorm partial of a quarter stays with ONE wave (gated: group 1, which holds the finished tiles; single: group 0,
+//     which reads group 1's six tiles back from LDS), summed over the 12 column tiles in the four-wave order; mean / rstd
+//     reach the other group through LDS;
+//   * both groups store: group g takes rows 8 g .. 8 g + 7 of its quarter, row-contiguous as before.
+// Every output element sees the four-wave kernels' operations in their order.  hipcc decides per code site which multiply-adds
+// it fuses, so these bodies are compiled with contraction OFF and spell out the fused multiply-adds of the four-wave kernels'
+// ISA (o += s (y + b); d = fma(s1, -1/192, o); s2 = fma(d, d, s2); q = fma(t, -1/4, m); M2; the rsqrt argument; the LN output).
+// The vmcnt rule of the file header holds: no store is issued before the last load of an iteration.
+// =====================================================================================================================
+constexpr int G2_THREADS = 512;
+static_assert(WS_FWD_LDS <= 160 * 1024 && WS_BWD_LDS <= 160 * 1024, "the CU has 160 KiB of LDS: no room for another buffer");
+
+template <int NA>
+struct G2Weights {
+    static constexpr int NTW = NA == 2 ? NT : 2;             // r-tiles of the down-type matrix (single: group 1 uses one)
+    static constexpr int NK = NA == 2 ? CT / 4 : CT / 8;     // column tiles of the up-type matrix
+    static constexpr int LOADS = NTW * (KS / 4) + NK + 2 * (NK / 2);      // vector loads per wave (g2_load_weights)
+    bf16x8 dn[NTW][KS / 4];
+    bf16x8 up01[NK];
+    bf16x8 up2[NK / 2];          // r = 32..47 of column tiles 2p (slots 0-3) and 2p+1 (slots 4-7)
+};
+static_assert(G2Weights<2>::LOADS == 42 && G2Weights<1>::LOADS == 24, "g2_load_weights changed: re-derive the counted wait");
+
+template <int NA>
+__device__ __forceinline__ void g2_load_weights(G2Weights<NA>& W, const void* dn, const void* up, int grp, int w4, int lane) {
+    constexpr int NTW = G2Weights<NA>::NTW, NK = G2Weights<NA>::NK;
+    const bf16* d = (const bf16*)dn;
+    const bf16* u = (const bf16*)up;
+#pragma unroll
+    for (int i = 0; i < NTW; ++i) {
+        // single: group 1's second slot repeats r-tile 2 -- loaded (both groups issue the same number of loads: the counted
+        // wait), never used
+        const int nt = NA == 2 ? i : (grp ? NT - 1 : i);
+#pragma unroll
+        for (int k = 0; k < KS / 4; ++k)
+            W.dn[i][k] = *reinterpret_cast<const bf16x8*>(d + ((nt * KS + w4 * (KS / 4) + k) * 64 + lane) * 8);
+    }
+    const int ct0 = w4 * (CT / 4) + (NA == 2 ? 0 : grp * NK);
+#pragma unroll
+    for (int k = 0; k < NK; ++k) W.up01[k] = *reinterpret_cast<const bf16x8*>(u + ((ct0 + k) * 64 + lane) * 8);
+#pragma unroll
+    for (int p = 0; p < NK / 2; ++p) {
+        const int ct = ct0 + 2 * p;
+        const bf16x4 lo = *reinterpret_cast<const bf16x4*>(u + CT * 64 * 8 + (ct * 64 + lane) * 4);
+        const bf16x4 hi = *reinterpret_cast<const bf16x4*>(u + CT * 64 * 8 + ((ct + 1) * 64 + lane) * 4);
+        W.up2[p] = bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+    }
+}
+// As ws_wait_tile0, for 8 waves: behind a wave's pieces of tile 0 come its weight loads (42 for one adapter of the gated
+// segment, 24 for its share of the single adapter) and its 6 pieces of tile 1 (the backward's saved-z piece of tile 1 is
+// not counted: the wait then covers one request more than it needs to).
+template <int NA>
+__device__ __forceinline__ void g2_wait_tile0(bool has_tile1) {
+    constexpr int behind = G2Weights<NA>::LOADS + 6;
+    static_assert(behind == (NA == 2 ? 48 : 30) && behind <= 63, "re-derive the counted wait (vmcnt holds 63)");
+    if (has_tile1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(behind) : "memory");
+    else FD_WAIT_VM0();
+}
+// one 16-token tile, HBM -> LDS by DMA: 48 row pieces of 1 KiB, 6 per wave (wave W: rows 2W, 2W+1)
+__device__ __forceinline__ void g2_tile_dma(const float* __restrict__ src, int nvalid, float* buf, int wave, int lane) {
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+        const int r = wave * 2 + j / 3, part = j % 3;
+        const int rr = r < nvalid ? r : nvalid - 1;       // rows past the segment end re-read its last row
+        ws_dma16(src + (size_t)rr * H + part * 256 + lane * 4, buf + r * ROWT + part * 256);
+    }
+}
+// saved-z tile of the backward: 6 DMA pieces, waves 0..5
+__device__ __forceinline__ void g2_ztile_dma(const float* __restrict__ zs, int nvalid, float* dst, int wave, int lane) {
+    if (wave < 6) {
+        const int fo = wave * 256 + lane * 4, r = fo / (2 * R), c = fo - r * (2 * R);
+        const int rr = r < nvalid ? r : nvalid - 1;
+        ws_dma16(zs + (size_t)rr * (2 * R) + c, dst + wave * 256);
+    }
+}
+// the two MFMAs of one column tile of an up-type product
+template <int NA>
+__device__ __forceinline__ f32x4 g2_up_tile(const G2Weights<NA>& W, int k, const bf16x8 b01, const bf16x8 (&b2)[2]) {
+    const f32x4 y = mfma16x32(W.up01[k], b01, f32x4{0.f, 0.f, 0.f, 0.f});
+    return mfma16x32(W.up2[k >> 1], b2[k & 1], y);
+}
+// K-split sum of slot s in the fixed order w = 0..3 (the four-wave layout of kspl: [w][6 slots][64 lanes])
+__device__ __forceinline__ f32x4 g2_ksum(const float* kspl, int s, int lane) {
+    f32x4 t = reinterpret_cast<const f32x4*>(kspl)[s * 64 + lane];
+#pragma unroll
+    for (int w = 1; w < 4; ++w) t = t + reinterpret_cast<const f32x4*>(kspl)[(w * 6 + s) * 64 + lane];
+    return t;
+}
+
+template <int NA>
+__device__ __forceinline__ void g2_fwd_body(const float* __restrict__ x, float* __restrict__ out,
+                                            const feddat_adapter_seg& sg, int t0, int tstep, int ntiles, float* smem,
+                                            const LnFuse& ln, float* __restrict__ z_save, const int dbg) {
+#pragma clang fp contract(off)
+    constexpr int NTW = G2Weights<NA>::NTW, NK = G2Weights<NA>::NK;
+    const int lane0 = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), grp = wave >> 2, w4 = wave & 3;
+    float* kspl = smem + 2 * TILE_F;
+    float* lnred = kspl + KSPL_F;              // 256 floats
+    float* sbu = lnred + 256;                  // [2][H]  up-projection biases
+    float* sbd = sbu + 2 * H;                  // [2][64] down-projection biases
+    float* sgam = sbd + 128;                   // [H] gamma, [H] beta of the fused LayerNorm
+    float* sbet = sgam + H;
+    if (t0 >= ntiles) return;                  // block-uniform: no group leaves alone
+    const int ad = NA == 2 ? grp : 0;          // this wave's adapter
+    const int ntc = NA == 2 ? NT : (grp ? 1 : 2);        // r-tiles this wave contracts: nt0 .. nt0 + ntc - 1
+    const int nt0 = NA == 2 ? 0 : 2 * grp;
+    const int kb = NA == 2 ? 0 : grp * NK;               // first column tile of the quarter this wave projects up
+    const int slot0 = ad * NT;                           // K-split slots of this wave's adapter (a * NT + nt)
+    const int lg = NA == 2 ? 1 : 0;                      // the group that ends up with a quarter's finished tiles: LayerNorm sums
+
+    // ---- prologue: as ws_fwd_body (tables, tile 0, weights, tile 1; only tile 0 is waited for by hand)
+    auto tile_dma = [&](int p) {
+        const int t = t0 + p * tstep;
+        if (t < ntiles && !(p && (dbg & 4))) {
+            const int row0 = sg.row_begin + t * 16;
+            const int nvalid = (sg.row_end - row0) < 16 ? (sg.row_end - row0) : 16;
+            g2_tile_dma(x + (size_t)(row0 + sg.x_row_delta) * H, nvalid, smem + p * TILE_F, wave, lane0);
+        }
+    };
+    for (int i = threadIdx.x; i < NA * H; i += G2_THREADS) sbu[i] = sg.bu[i / H][i % H];
+    if (threadIdx.x < NA * R) sbd[(threadIdx.x / R) * 64 + threadIdx.x % R] = sg.bd[threadIdx.x / R][threadIdx.x % R];
+    if (ln.gamma)
+        for (int i = threadIdx.x; i < H; i += G2_THREADS) {
+            sgam[i] = ln.gamma[i];
+            sbet[i] = ln.beta[i];
+        }
+    const float sc0 = sg.scale[0], sc1 = sg.scale[NA - 1];
+    tile_dma(0);
+    G2Weights<NA> W;
+    g2_load_weights<NA>(W, ad ? sg.wd[NA - 1] : sg.wd[0], ad ? sg.wu[NA - 1] : sg.wu[0], grp, w4, lane0);
+    tile_dma(1);
+    g2_wait_tile0<NA>(!(dbg & 4) && t0 + tstep < ntiles);
+    __syncthreads();
+
+    // Steady state as in ws_fwd_body: compute -> vmcnt(0) -> stores of tile t -> barrier -> DMA of tile t+2.
+    int cur = 0;
+    for (int t = t0; t < ntiles; t += tstep, cur ^= 1) {
+        const int row0 = sg.row_begin + t * 16;
+        const int nvalid = (sg.row_end - row0) < 16 ? (sg.row_end - row0) : 16;
+        float* buf = smem + cur * TILE_F;
+        // lane-derived LDS and global offsets are re-derived per tile from a laundered lane id: hoisted out of the loop they
+        // cost more registers than the 256 a wave has next to its 144 weight dwords
+        int lane = lane0;
+        asm volatile("" : "+v"(lane));
+        const int g = lane >> 4, i16 = lane & 15;
+
+        f32x4 z_keep = f32x4{0.f, 0.f, 0.f, 0.f};
+        float mean = 0.f, rstd = 0.f;
+        if (!(dbg & 2)) {
+        // 1. down-projection of this wave's feature quarter for its adapter (gated) / its r-tiles (single)
+        float* frag = buf + i16 * ROWT + w4 * WCOLS + 4 * g;
+        f32x4 xk[CT / 4];
+        f32x4 z[NTW];
+#pragma unroll
+        for (int i = 0; i < NTW; ++i) z[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+        if constexpr (NA == 2) {
+#pragma unroll
+            for (int k = 0; k < KS / 4; ++k) {
+                const bf16x8 xf = cvt8(*reinterpret_cast<const f32x4*>(frag + k * 32), *reinterpret_cast<const f32x4*>(frag + k * 32 + 16));
+#pragma unroll
+                for (int i = 0; i < NTW; ++i) z[i] = mfma16x32(W.dn[i][k], xf, z[i]);
+            }
+        } else {
+            bf16x8 xf[KS / 4];
+#pragma unroll
+            for (int k = 0; k < KS / 4; ++k) {
+                xf[k] = cvt8(*reinterpret_cast<const f32x4*>(frag + k * 32), *reinterpret_cast<const f32x4*>(frag + k * 32 + 16));
+                z[0] = mfma16x32(W.dn[0][k], xf[k], z[0]);
+            }
+            if (ntc == 2) {
+#pragma unroll
+                for (int k = 0; k < KS / 4; ++k) z[1] = mfma16x32(W.dn[1][k], xf[k], z[1]);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < NTW; ++i)
+            if (NA == 2 || i < ntc) reinterpret_cast<f32x4*>(kspl)[(w4 * 6 + slot0 + nt0 + i) * 64 + lane] = z[i];
+        __syncthreads();
+
+        // 2. K-split sums of this wave's adapter, bias, ReLU (every wave: all three r-tiles)
+        f32x4 zz[NT];
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) {
+            const f32x4 tsum = g2_ksum(kspl, slot0 + nt, lane);
+            const f32x4 b4 = *reinterpret_cast<const f32x4*>(sbd + ad * 64 + nt * 16 + 4 * g);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) zz[nt][e] = fmaxf(tsum[e] + b4[e], 0.f);
+            if (nt == w4) z_keep = zz[nt];         // quarter nt stores r-tile nt (with the other stores, below)
+        }
+        const bf16x8 zb01 = cvt8(zz[0], zz[1]);
+        const bf16x8 zb2[2] = {pad8(zz[2]), pad8hi(zz[2])};
+
+        // 3. up-projection on top of the residual x
+        if constexpr (NA == 2) {
+            // gated: 12 column tiles of this wave's adapter.  o = (x + s0 (y0 + b0)) + s1 (y1 + b1), the four-wave order: group 0
+            // adds its term to the residual in place in the tile buffer (after the barrier above only quarter w4 of group 0
+            // touches these fragments), group 1 keeps its y tiles in registers until group 0 is through, then adds its term and
+            // holds the finished tiles for the LayerNorm sums.  (The products are common code of both groups: as two arms of a
+            // branch their 48 result registers are allocated twice.)
+#pragma unroll
+            for (int k = 0; k < CT / 4; ++k) xk[k] = g2_up_tile<NA>(W, k, zb01, zb2);
+            if (!grp) {
+#pragma unroll
+                for (int k = 0; k < CT / 4; ++k) {
+                    f32x4 o = *reinterpret_cast<const f32x4*>(frag + k * 16);
+                    const f32x4 bu4 = *reinterpret_cast<const f32x4*>(sbu + (w4 * (CT / 4) + k) * 16 + 4 * g);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) o[e] = __builtin_fmaf(sc0, xk[k][e] + bu4[e], o[e]);
+                    *reinterpret_cast<f32x4*>(frag + k * 16) = o;
+                }
+            }
+            __syncthreads();
+            if (grp) {
+#pragma unroll
+                for (int k = 0; k < CT / 4; ++k) {
+                    f32x4 o = *reinterpret_cast<const f32x4*>(frag + k * 16);
+                    const f32x4 bu4 = *reinterpret_cast<const f32x4*>(sbu + H + (w4 * (CT / 4) + k) * 16 + 4 * g);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) o[e] = __builtin_fmaf(sc1, xk[k][e] + bu4[e], o[e]);
+                    xk[k] = o;
+                    *reinterpret_cast<f32x4*>(frag + k * 16) = o;
+                }
+            }
+        } else {
+            // single: column tiles kb .. kb + 5 of the quarter, finished in place in the tile buffer (only their owner reads
+            // the residual of a tile after the barrier above)
+#pragma unroll
+            for (int i = 0; i < NK; ++i) {
+                f32x4 o = *reinterpret_cast<const f32x4*>(frag + (kb + i) * 16);
+                const f32x4 y = g2_up_tile<NA>(W, i, zb01, zb2);
+                const f32x4 bu4 = *reinterpret_cast<const f32x4*>(sbu + (w4 * (CT / 4) + kb + i) * 16 + 4 * g);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) o[e] = __builtin_fmaf(sc0, y[e] + bu4[e], o[e]);
+                xk[i] = o;
+                *reinterpret_cast<f32x4*>(frag + (kb + i) * 16) = o;
+            }
+            __syncthreads();
+            if (ln.gamma && grp == lg) {           // group 0 sums the whole quarter: group 1's six tiles come back from LDS
+#pragma unroll
+                for (int i = 0; i < NK; ++i) xk[NK + i] = *reinterpret_cast<const f32x4*>(frag + (NK + i) * 16);
+            }
+        }
+
+        // 4. LayerNorm statistics as in ws_fwd_body (one wave per quarter: group lg), with that kernel's fused multiply-adds
+        if (ln.gamma) {
+            if (grp == lg) {
+                float s1 = 0.f;
+#pragma unroll
+                for (int k = 0; k < CT / 4; ++k) {
+                    const f32x4 o = xk[k];
+                    s1 += (o[0] + o[1]) + (o[2] + o[3]);
+                }
+                s1 += __shfl_xor(s1, 16, 64);
+                s1 += __shfl_xor(s1, 32, 64);
+                const float mw = s1 * (1.0f / WCOLS);
+                // (0 + d0 d0) + d1 d1 is where hipcc had a choice in ws_fwd_body, and it fused the FIRST product: fma(d0, d0, d1 d1)
+                const float d0 = __builtin_fmaf(s1, -(1.0f / WCOLS), xk[0][0]), d1 = __builtin_fmaf(s1, -(1.0f / WCOLS), xk[0][1]);
+                float s2 = __builtin_fmaf(d0, d0, d1 * d1);
+#pragma unroll
+                for (int k = 0; k < CT / 4; ++k)
+#pragma unroll
+                    for (int e = k ? 0 : 2; e < 4; ++e) {
+                        const float d = __builtin_fmaf(s1, -(1.0f / WCOLS), xk[k][e]);
+                        s2 = __builtin_fmaf(d, d, s2);
+                    }
+                s2 += __shfl_xor(s2, 16, 64);
+                s2 += __shfl_xor(s2, 32, 64);
+                if (g == 0) {
+                    lnred[w4 * 32 + 2 * i16] = mw;
+                    lnred[w4 * 32 + 2 * i16 + 1] = s2;
+                }
+            }
+            __syncthreads();
+            if (grp == lg) {
+                const float m0 = lnred[2 * i16], m1 = lnred[32 + 2 * i16], m2 = lnred[64 + 2 * i16], m3 = lnred[96 + 2 * i16];
+                const float ms = (m0 + m1) + (m2 + m3);
+                mean = ms * 0.25f;
+                const float q0 = __builtin_fmaf(ms, -0.25f, m0), q1 = __builtin_fmaf(ms, -0.25f, m1),
+                            q2 = __builtin_fmaf(ms, -0.25f, m2), q3 = __builtin_fmaf(ms, -0.25f, m3);
+                const float M2 = __builtin_fmaf((float)WCOLS, (q0 * q0 + q1 * q1) + (q2 * q2 + q3 * q3),
+                                                (lnred[2 * i16 + 1] + lnred[32 + 2 * i16 + 1]) +
+                                                    (lnred[64 + 2 * i16 + 1] + lnred[96 + 2 * i16 + 1]));
+                rstd = rsqrtf(__builtin_fmaf(M2, 1.0f / H, ln.eps));
+                if (g == 0) {
+                    lnred[128 + w4 * 32 + 2 * i16] = mean;
+                    lnred[128 + w4 * 32 + 2 * i16 + 1] = rstd;
+                }
+            }
+        }
+
+        // 5. outputs: the finished tiles are in the tile buffer in fragment layout -> row-contiguous stores by both groups,
+        // behind a barrier: each group stores rows that the other wrote
+        __syncthreads();
+        }
+        float* orow = out + (size_t)row0 * H + w4 * WCOLS;
+        const float* srow = buf + w4 * WCOLS;
+        constexpr int NLG = NLD / 2;           // accesses per lane: rows 8 grp .. 8 grp + 7 of the quarter
+        f32x4 v[NLG];
+#pragma unroll
+        for (int j = 0; j < NLG; ++j) {
+            const int r = 8 * grp + 4 * (j / 3) + g, c = 16 * (j % 3) + i16;
+            v[j] = *reinterpret_cast<const f32x4*>(srow + r * ROWT + c * 4);
+        }
+        FD_WAIT_VM0();                         // next tile's DMA has landed; no store is issued before this point
+        const bool st_on = !(dbg & 1);
+        auto emit = [&](auto full_tag) {       // full tiles: no per-access predicates (see ws_fwd_body)
+#pragma clang fp contract(off)
+            constexpr bool FULL = decltype(full_tag)::value;
+            if (z_save && w4 < NT && (NA == 2 || !grp) && (FULL || i16 < nvalid))
+                *reinterpret_cast<f32x4*>(z_save + (size_t)(row0 + i16) * (2 * R) + ad * R + w4 * 16 + 4 * g) = z_keep;
+#pragma unroll
+            for (int j = 0; j < NLG; ++j) {
+                const int r = 8 * grp + 4 * (j / 3) + g, c = 16 * (j % 3) + i16;
+                if (FULL || r < nvalid) *reinterpret_cast<f32x4*>(orow + (size_t)r * H + c * 4) = v[j];
+            }
+            if (ln.gamma) {
+                bf16* yrow = ln.y16 + (size_t)row0 * H + w4 * WCOLS;
+#pragma unroll
+                for (int j = 0; j < NLG; ++j) {
+                    const int r = 8 * grp + 4 * (j / 3) + g, c = 16 * (j % 3) + i16;
+                    const float m = lnred[128 + w4 * 32 + 2 * r], rs = lnred[128 + w4 * 32 + 2 * r + 1];
+                    const f32x4 gm = *reinterpret_cast<const f32x4*>(sgam + w4 * WCOLS + c * 4);
+                    const f32x4 bt = *reinterpret_cast<const f32x4*>(sbet + w4 * WCOLS + c * 4);
+                    f32x4 y;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) y[e] = __builtin_fmaf((v[j][e] - m) * rs, gm[e], bt[e]);
+                    if (FULL || r < nvalid) *reinterpret_cast<bf16x4*>(yrow + (size_t)r * H + c * 4) = cvt4(y);
+                }
+                if (grp == lg && w4 == 0 && g == 0 && (FULL || i16 < nvalid) && ln.stats) {
+                    ln.stats[2 * (size_t)(row0 + i16)] = mean;
+                    ln.stats[2 * (size_t)(row0 + i16) + 1] = rstd;
+                }
+            }
+        };
+        if (st_on) {
+            if (nvalid == 16) emit(std::true_type{});
+            else emit(std::false_type{});
+        }
+        __syncthreads();                       // every wave: next tile visible, this buffer consumed
+        if (t + 2 * tstep < ntiles && !(dbg & 4)) {
+            const int rn = sg.row_begin + (t + 2 * tstep) * 16;
+            const int nv = (sg.row_end - rn) < 16 ? (sg.row_end - rn) : 16;
+            g2_tile_dma(x + (size_t)(rn + sg.x_row_delta) * H, nv, buf, wave, lane);
+        }
+    }
+}
+
+__global__ __launch_bounds__(G2_THREADS, 1) void adapter_fwd_g2_kernel(const float* __restrict__ x, float* __restrict__ out,
+                                                                       WsLaunch L, LnFuse ln, float* __restrict__ z_save) {
+    extern __shared__ __attribute__((aligned(16))) float ws_smem[];
+    int s, t0, tstep, ntiles;
+    ws_walk(L, s, t0, tstep, ntiles);
+    const feddat_adapter_seg& sg = L.a.seg[s];
+    if (sg.n_adapters == 2) g2_fwd_body<2>(x, out, sg, t0, tstep, ntiles, ws_smem, ln, z_save, FD_ABL(L.dbg));
+    else g2_fwd_body<1>(x, out, sg, t0, tstep, ntiles, ws_smem, ln, z_save, FD_ABL(L.dbg));
+}
+
+// Backward, z saved by the forward (the fp8 copy of dx stays on adapter_bwd_ws_kernel<true>).  Group a: g = Wu[a]^T dy, dz[a],
+// y[a] = Wd[a]^T dz[a]; gated: dx = (dy + y0) + y1, the four-wave order, group 0's add in place in LDS, then group 1's (it holds
+// its y tiles in registers meanwhile: nothing else is live next to the weights); single: by r-tile and column tile.
+template <int NA>
+__device__ __forceinline__ void g2_bwd_body(const float* __restrict__ dy, float* __restrict__ dx, bf16* __restrict__ dx16,
+                                            float* __restrict__ z_out, float* __restrict__ dz_out,
+                                            const feddat_adapter_seg& sg, int t0, int tstep, int ntiles, float* smem,
+                                            const float* __restrict__ z_saved, const int dbg) {
+#pragma clang fp contract(off)
+    constexpr int NTW = G2Weights<NA>::NTW, NK = G2Weights<NA>::NK;
+    const int lane0 = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), grp = wave >> 2, w4 = wave & 3;
+    float* kspl = smem + 2 * TILE_F;
+    float* ztile = kspl + KSPL_F;              // [2][ZT_F]
+    if (t0 >= ntiles) return;                  // block-uniform
+    const int ad = NA == 2 ? grp : 0;
+    const int ntc = NA == 2 ? NT : (grp ? 1 : 2);
+    const int nt0 = NA == 2 ? 0 : 2 * grp;
+    const int kb = NA == 2 ? 0 : grp * NK;
+    const int slot0 = ad * NT;
+    auto tile_dma = [&](int p) {       // prologue order and waits as in g2_fwd_body
+        const int t = t0 + p * tstep;
+        if (t < ntiles && !(p && (dbg & 4))) {
+            const int row0 = sg.row_begin + t * 16;
+            const int nvalid = (sg.row_end - row0) < 16 ? (sg.row_end - row0) : 16;
+            g2_tile_dma(dy + (size_t)row0 * H, nvalid, smem + p * TILE_F, wave, lane0);
+            g2_ztile_dma(z_saved + (size_t)row0 * (2 * R), nvalid, ztile + p * ZT_F, wave, lane0);
+        }
+    };
+    tile_dma(0);
+    G2Weights<NA> W;
+    g2_load_weights<NA>(W, ad ? sg.wuT[NA - 1] : sg.wuT[0], ad ? sg.wdT[NA - 1] : sg.wdT[0], grp, w4, lane0);
+    tile_dma(1);
+    const float sca = ad ? sg.scale[NA - 1] : sg.scale[0];
+    const int train_slot = sg.train_slot;
+    const bool exp_z = train_slot == ad && (NA == 2 || !grp) && w4 < NT && z_out;   // the trainable slot's group exports z, dz
+    g2_wait_tile0<NA>(!(dbg & 4) && t0 + tstep < ntiles);
+    __syncthreads();
+
+    int cur = 0;      // pipeline order as in ws_fwd_body
+    for (int t = t0; t < ntiles; t += tstep, cur ^= 1) {
+        const int row0 = sg.row_begin + t * 16;
+        const int nvalid = (sg.row_end - row0) < 16 ? (sg.row_end - row0) : 16;
+        float* buf = smem + cur * TILE_F;
+        // lane-derived LDS and global offsets are re-derived per tile from a laundered lane id: hoisted out of the loop they
+        // cost more registers than the 256 a wave has next to its 144 weight dwords
+        int lane = lane0;
+        asm volatile("" : "+v"(lane));
+        const int g = lane >> 4, i16 = lane & 15;
+        float* zt = ztile + cur * ZT_F;
+
+        f32x4 z_keep = f32x4{0.f, 0.f, 0.f, 0.f}, dz_keep = z_keep;
+        if (!(dbg & 2)) {
+        // g = Wu^T dy over this wave's feature quarter, K-split reduce
+        float* frag = buf + i16 * ROWT + w4 * WCOLS + 4 * g;
+        f32x4 gr[NTW];
+#pragma unroll
+        for (int i = 0; i < NTW; ++i) gr[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+        if constexpr (NA == 2) {
+#pragma unroll
+            for (int k = 0; k < KS / 4; ++k) {
+                const bf16x8 df = cvt8(*reinterpret_cast<const f32x4*>(frag + k * 32), *reinterpret_cast<const f32x4*>(frag + k * 32 + 16));
+#pragma unroll
+                for (int i = 0; i < NTW; ++i) gr[i] = mfma16x32(W.dn[i][k], df, gr[i]);
+            }
+        } else {
+            bf16x8 df[KS / 4];
+#pragma unroll
+            for (int k = 0; k < KS / 4; ++k) {
+                df[k] = cvt8(*reinterpret_cast<const f32x4*>(frag + k * 32), *reinterpret_cast<const f32x4*>(frag + k * 32 + 16));
+                gr[0] = mfma16x32(W.dn[0][k], df[k], gr[0]);
+            }
+            if (ntc == 2) {
+#pragma unroll
+                for (int k = 0; k < KS / 4; ++k) gr[1] = mfma16x32(W.dn[1][k], df[k], gr[1]);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < NTW; ++i)
+            if (NA == 2 || i < ntc) reinterpret_cast<f32x4*>(kspl)[(w4 * 6 + slot0 + nt0 + i) * 64 + lane] = gr[i];
+        __syncthreads();
+
+        // dz = scale * g * (z > 0); z and dz of the trainable slot go out for the weight gradients
+        f32x4 dzv[NT];
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) {
+            const f32x4 gs = g2_ksum(kspl, slot0 + nt, lane);
+            const f32x4 zz = *reinterpret_cast<const f32x4*>(zt + i16 * (2 * R) + ad * R + nt * 16 + 4 * g);
+            f32x4 dz;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) dz[e] = zz[e] > 0.f ? sca * gs[e] : 0.f;
+            dzv[nt] = dz;
+            if (nt == w4) {
+                z_keep = zz;
+                dz_keep = dz;
+            }
+        }
+        const bf16x8 dzb01 = cvt8(dzv[0], dzv[1]);
+        const bf16x8 dzb2[2] = {pad8(dzv[2]), pad8hi(dzv[2])};
+        if (dx) {
+            if constexpr (NA == 2) {
+                // dx = (dy + y0) + y1: group 0 adds its tiles to the dy fragments in place (only quarter w4 of group 0 touches them
+                // after the barrier above), group 1 keeps its y tiles in registers until group 0 is through, then adds them on top
+                // (the products are common code of both groups: as two arms of a branch the 48 result registers are allocated twice)
+                f32x4 y[CT / 4];
+#pragma unroll
+                for (int k = 0; k < CT / 4; ++k) y[k] = g2_up_tile<NA>(W, k, dzb01, dzb2);
+                if (!grp) {
+#pragma unroll
+                    for (int k = 0; k < CT / 4; ++k) {
+                        const f32x4 o = *reinterpret_cast<const f32x4*>(frag + k * 16) + y[k];
+                        *reinterpret_cast<f32x4*>(frag + k * 16) = o;
+                    }
+                }
+                __syncthreads();
+                if (grp) {
+#pragma unroll
+                    for (int k = 0; k < CT / 4; ++k) {
+                        const f32x4 o = *reinterpret_cast<const f32x4*>(frag + k * 16) + y[k];
+                        *reinterpret_cast<f32x4*>(frag + k * 16) = o;
+                    }
+                }
+            } else {
+#pragma unroll
+                for (int i = 0; i < NK; ++i) {
+                    const f32x4 o = *reinterpret_cast<const f32x4*>(frag + (kb + i) * 16) + g2_up_tile<NA>(W, i, dzb01, dzb2);
+                    *reinterpret_cast<f32x4*>(frag + (kb + i) * 16) = o;
+                }
+            }
+            __syncthreads();                   // both groups store rows that either wrote
+        }
+        }
+        constexpr int NLG = NLD / 2;
+        f32x4 v[NLG];
+        if (dx) {
+            const float* srow = buf + w4 * WCOLS;
+#pragma unroll
+            for (int j = 0; j < NLG; ++j) {
+                const int r = 8 * grp + 4 * (j / 3) + g, c = 16 * (j % 3) + i16;
+                v[j] = *reinterpret_cast<const f32x4*>(srow + r * ROWT + c * 4);
+            }
+        }
+        FD_WAIT_VM0();                         // next tile's DMA has landed; no store is issued before this point
+        const bool st_on = !(dbg & 1);
+        auto emit = [&](auto full_tag) {        // full tiles: no per-access predicates (see ws_fwd_body)
+            constexpr bool FULL = decltype(full_tag)::value;
+            if (exp_z && (FULL || i16 < nvalid)) {
+                *reinterpret_cast<f32x4*>(z_out + (size_t)(row0 + i16) * R + w4 * 16 + 4 * g) = z_keep;
+                *reinterpret_cast<f32x4*>(dz_out + (size_t)(row0 + i16) * R + w4 * 16 + 4 * g) = dz_keep;
+            }
+            if (dx) {
+                float* orow = dx + (size_t)row0 * H + w4 * WCOLS;
+#pragma unroll
+                for (int j = 0; j < NLG; ++j) {
+                    const int r = 8 * grp + 4 * (j / 3) + g, c = 16 * (j % 3) + i16;
+                    if (FULL || r < nvalid) *reinterpret_cast<f32x4*>(orow + (size_t)r * H + c * 4) = v[j];
+                }
+                if (dx16) {
+                    bf16* brow = dx16 + (size_t)row0 * H + w4 * WCOLS;
+#pragma unroll
+                    for (int j = 0; j < NLG; ++j) {
+                        const int r = 8 * grp + 4 * (j / 3) + g, c = 16 * (j % 3) + i16;
+                        if (FULL || r < nvalid) *reinterpret_cast<bf16x4*>(brow + (size_t)r * H + c * 4) = cvt4(v[j]);
+                    }
+                }
+            }
+        };
+        if (st_on) {
+            if (nvalid == 16) emit(std::true_type{});
+            else emit(std::false_type{});
+        }
+        __syncthreads();                       // every wave: next tile visible, this buffer consumed
+        if (t + 2 * tstep < ntiles && !(dbg & 4)) {
+            const int rn = sg.row_begin + (t + 2 * tstep) * 16;
+            const int nv = (sg.row_end - rn) < 16 ? (sg.row_end - rn) : 16;
+            g2_tile_dma(dy + (size_t)rn * H, nv, buf, wave, lane);
+            g2_ztile_dma(z_saved + (size_t)rn * (2 * R), nv, zt, wave, lane);
+        }
+    }
+}
+
+__global__ __launch_bounds__(G2_THREADS, 1) void adapter_bwd_g2_kernel(const float* __restrict__ dy, float* __restrict__ dx,
+                                                                       bf16* __restrict__ dx16, float* __restrict__ z_out,
+                                                                       float* __restrict__ dz_out, WsLaunch L,
+                                                                       const float* __restrict__ z_saved) {
+    extern __shared__ __attribute__((aligned(16))) float ws_smem[];
+    int s, t0, tstep, ntiles;
+    ws_walk(L, s, t0, tstep, ntiles);
+    const feddat_adapter_seg& sg = L.a.seg[s];
+    if (sg.n_adapters == 2) g2_bwd_body<2>(dy, dx, dx16, z_out, dz_out, sg, t0, tstep, ntiles, ws_smem, z_saved, FD_ABL(L.dbg));
+    else g2_bwd_body<1>(dy, dx, dx16, z_out, dz_out, sg, t0, tstep, ntiles, ws_smem, z_saved, FD_ABL(L.dbg));
+}
+
+// host: blocks per segment, proportional to the tiles (at least one block per non-empty segment, one block per CU in all).
+// g0 weighs a tile of either segment the same, also with the two-group kernels.  Pure arithmetic at the step's shape: 370 + 370
+// tiles on 256 blocks are 2.9 tiles per block on either side, so both sides take three rounds; a side only gets down to two
+// rounds with >= 185 blocks, which pushes the other side (71 blocks) to six.  Any g0 in 124..132 gives the same 3 + 3 rounds,
+// so a moderate difference between the two segments' per-tile costs (not measured apart) cannot pay under this quantisation.
 int ws_plan(const AdapterLaunch& A, int tiles, WsLaunch& L, int& grid) {
     int n_cu = 0;
     const int rc = fd_device_cus(&n_cu);
@@ -983,9 +1556,15 @@ int ws_launch_fwd(const float* x, float* out, const AdapterLaunch& A, int tiles,
     int grid;
     int rc = ws_plan(A, tiles, W, grid);
     if (rc) return rc;
-    rc = fd_set_max_lds((const void*)adapter_fwd_ws_kernel, WS_FWD_LDS);
+    if (fd_debug_flags() & FD_DEBUG_ADAPTER_4W) {       // A/B: the four-wave kernel (bit-identical)
+        rc = fd_set_max_lds((const void*)adapter_fwd_ws_kernel, WS_FWD_LDS);
+        if (rc) return rc;
+        hipLaunchKernelGGL(adapter_fwd_ws_kernel, dim3(grid), dim3(256), WS_FWD_LDS, stream, x, out, W, ln, z_save);
+        FD_LAUNCH_RET();
+    }
+    rc = fd_set_max_lds((const void*)adapter_fwd_g2_kernel, WS_FWD_LDS);
     if (rc) return rc;
-    hipLaunchKernelGGL(adapter_fwd_ws_kernel, dim3(grid), dim3(256), WS_FWD_LDS, stream, x, out, W, ln, z_save);
+    hipLaunchKernelGGL(adapter_fwd_g2_kernel, dim3(grid), dim3(G2_THREADS), WS_FWD_LDS, stream, x, out, W, ln, z_save);
     FD_LAUNCH_RET();
 }
 
@@ -1035,11 +1614,16 @@ static int adapter_bwd_launch(const float* x, const float* z_saved, const float*
             if (rc3) return rc3;
             hipLaunchKernelGGL(adapter_bwd_ws_kernel<true>, dim3(grid), dim3(256), WS_BWD_LDS, stream, dy, dx, (bf16*)dx_bf16,
                                z_out, dz_out, W, z_saved, (unsigned char*)dx_fp8, dx_scale);
-        } else {
+        } else if (fd_debug_flags() & FD_DEBUG_ADAPTER_4W) {       // A/B: the four-wave kernel (bit-identical)
             const int rc3 = fd_set_max_lds((const void*)adapter_bwd_ws_kernel<false>, WS_BWD_LDS);
             if (rc3) return rc3;
             hipLaunchKernelGGL(adapter_bwd_ws_kernel<false>, dim3(grid), dim3(256), WS_BWD_LDS, stream, dy, dx, (bf16*)dx_bf16,
                                z_out, dz_out, W, z_saved, (unsigned char*)nullptr, (float*)nullptr);
+        } else {
+            const int rc3 = fd_set_max_lds((const void*)adapter_bwd_g2_kernel, WS_BWD_LDS);
+            if (rc3) return rc3;
+            hipLaunchKernelGGL(adapter_bwd_g2_kernel, dim3(grid), dim3(G2_THREADS), WS_BWD_LDS, stream, dy, dx, (bf16*)dx_bf16,
+                               z_out, dz_out, W, z_saved);
         }
     } else {
         hipLaunchKernelGGL(adapter_bwd_kernel<false>, dim3(tiles), dim3(256), dbg_extra_lds(), stream, x, dy, dx,

@@ -63,13 +63,15 @@ int fd_set_max_lds(const void* kernel, int bytes);     // hipFuncAttributeMaxDyn
 // fused kernel's and whose dQ is NOT: role 1 recomputes the scores in the transposed orientation and sums D = sum_d dO O in another
 // order; equally accurate, tests/test_attention_kernels_gpu.py holds both to the same per-element bound), 1 | 2 together the DUAL form of the persistent GEMM (two independent 128 x 192 workgroups per CU; with 64:
 // only where it has at least two rounds of tiles), 32 / 64 force 192- / 256-row tiles, 128 no small-tile kernel, 256 the K = 32 fp8 MFMA, bit 23 one
-// attention-backward block per pair (the same kernel as the persistent grid: bit-identical for every pair count, ragged last round included), bit 27 no 160-row GEMM tiles, bits 28..31 cap the persistent GEMM grid at 16 x value workgroups.
+// attention-backward block per pair (the same kernel as the persistent grid: bit-identical for every pair count, ragged last round included), bit 27 no 160-row GEMM tiles, bits 28..31 cap the persistent GEMM grid at 16 x value workgroups,
+// bit 11 (FD_DEBUG_ADAPTER_4W) the four-wave weight-stationary adapter kernels instead of the two-wave-group ones (adapter.hip; bit-identical).
 #ifdef FEDDAT_ABLATE
 #define FD_ABL(x) (x)
 #else
 #define FD_ABL(x) 0
 #endif
-constexpr unsigned FD_DEBUG_SELECT_BITS = 1u | 2u | 32u | 64u | 128u | 256u | (1u << 23) | (1u << 27) | (0xfu << 28);
+constexpr unsigned FD_DEBUG_ADAPTER_4W = 1u << 11;
+constexpr unsigned FD_DEBUG_SELECT_BITS = 1u | 2u | 32u | 64u | 128u | 256u | FD_DEBUG_ADAPTER_4W | (1u << 23) | (1u << 27) | (0xfu << 28);
 int fd_debug_flags();                                  // ablation flags (feddat_set_debug_flags), 0 in production
 int fd_prepare_all_kernels();                          // sets every kernel's LDS attribute on the current device
 int fd_prepare_gemm_kernels();

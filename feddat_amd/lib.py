@@ -294,8 +294,9 @@ def set_debug_flags(flags: int):
     S <= 192: equally accurate, not bit-identical; its dK | dV are): 1 / 2 GEMMs on the two-group / one-wave-per-SIMD kernel, 32 / 64
     force 192- / 256-row tiles, 128 no small-tile kernel, 256 K = 32 fp8 MFMA, bit 23 one attention-backward block per pair,
     bits 28..31 cap the persistent GEMM grid, 1 | 2 together the dual form of the persistent GEMM (what they do to a given
-    GEMM launch: gemm_route).  The timing-only ablations (8 skip epilogue, 4 / 16, 512, bits 8..22, 24..26)
-    exist in the ablation build only (use_ablation_build)."""
+    GEMM launch: gemm_route), bit 11 (2048) the four-wave weight-stationary adapter kernels instead of the two-wave-group
+    ones.  The timing-only ablations (8 skip epilogue, 4 / 16, 512, bits 8..22, 24..26) exist in the ablation build only
+    (use_ablation_build); there bit 11 is also part of the GEMM block cap (bits 8..19), which only GEMM launches read."""
     _chk(load().feddat_set_debug_flags(int(flags)), "feddat_set_debug_flags")
 
 

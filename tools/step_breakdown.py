@@ -95,7 +95,7 @@ def main():
     ap.add_argument("--debug-flags", type=lambda v: int(v, 0), default=0, help="feddat_set_debug_flags value (ablations)")
     args = ap.parse_args()
     from feddat_amd import engine, lib as L, vilt_spec
-    if args.debug_flags & ~(1 | 2 | 32 | 64 | 128 | 256 | (1 << 23) | (0xf << 28)):
+    if args.debug_flags & ~(1 | 2 | 32 | 64 | 128 | 256 | (1 << 11) | (1 << 23) | (0xf << 28)):
         if args.operands != "bf16":      # the ablation build exists for bf16 operands only: say so instead of timing un-ablated kernels
             raise SystemExit("timing-only ablation flags need --operands bf16 (libfeddat_hip_ablate.so is a bf16-operand build)")
         L.use_ablation_build()      # timing-only probes: libfeddat_hip_ablate.so (python -m feddat_amd.build --ablate)
