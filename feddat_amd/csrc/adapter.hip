@@ -2,21 +2,39 @@
 // Reference: src/modeling/models/adapter.py:124-163 (single: 125-131; gating: 133-146, get_agg_out 118-122),
 // called as adapter(h, h) from Adaptered_ViltOutput.forward (src/modeling/adaptered_output.py:77).
 //
-// One block (4 waves) owns 16 tokens; wave w owns features / output columns [192 w, 192 w + 192) of them.
+// Map of the file: three forms of the kernel, every one of them working on 16-token tiles, all computing the same bits.
+//   1. ONE TILE PER BLOCK, z recomputed from x (bwd_body, adapter_bwd_kernel; 4 waves).  Production: what
+//      feddat_adapter_bwd launches when the caller has no saved z (z_saved == NULL; vilt_layer.hip, the tests).
+//   2. FOUR-WAVE WEIGHT-STATIONARY, persistent, tiles streamed through LDS (ws_fwd_body / ws_bwd_body; adapter_fwd_ws_kernel,
+//      adapter_bwd_ws_kernel<Q8>).  adapter_bwd_ws_kernel<true> is production: the backward with the fp8 copy of dx
+//      (feddat_adapter_bwd_fp8).  The forward and adapter_bwd_ws_kernel<false> run only under debug flag
+//      FD_DEBUG_ADAPTER_4W: they are the bit-identity reference of tests/test_adapter_two_groups_gpu.py.
+//   3. TWO WAVE GROUPS per block, weights split between the groups (g2_fwd_body / g2_bwd_body; adapter_fwd_g2_kernel,
+//      adapter_bwd_g2_kernel; 8 waves).  Production: every other launch.
+// Forms 2 and 3 are built from ONE set of streaming helpers (section "Streaming forms": LDS plan, tile / saved-z DMA, counted
+// prologue wait, register-resident weight quarter, per-tile row arithmetic, prefetch tail, table prologue, block walk, launch),
+// parameterised by the waves per block NW = 4 or 8.  Whether a piece of code may be shared is decided by the kernels' ISA,
+// not by taste: a merge that moves a production kernel's instructions is not made.  That is why the row read-back and the
+// stores, the prologue's tile_dma lambdas and the four-wave backward's K-split sums are still written out in the bodies;
+// profiles/r09_adapter_refactor_isa.txt lists every merge that was tried and dropped, and why.
+//
+// Common to all forms.  In a tile, wave quarter w owns features / output columns [192 w, 192 w + 192).
 //   * HBM <-> registers is ROW-CONTIGUOUS: a wave moves its [16 x 192] fp32 slice with 12 x 16-byte accesses per lane in
 //     which consecutive lanes touch consecutive addresses (runs of 768 B).  The MFMA operand / accumulator layout wants
 //     lane & 15 = token, i.e. 16 different rows per 16-lane group -- loading or storing in THAT layout makes every
 //     wave instruction 64 separate 16-byte L1 accesses (measured: TCP_TOTAL_CACHE_ACCESSES 26-32 per VMEM instruction,
-//     the L1 tag pipeline busy for the whole kernel), so the slice is transposed through a per-wave LDS tile instead
-//     (800-byte rows: fragment reads conflict-free).
+//     the L1 tag pipeline busy for the whole kernel), so the slice is transposed through LDS instead (form 1: a per-wave
+//     tile of 800-byte rows; forms 2 and 3: the streamed tile, 776-float rows; fragment reads conflict-free in both).
 //   * The [16 x 48] bottleneck never reaches HBM: the down-projection is computed as Z^T[r, tok] so that its
 //     accumulator layout (lane: token = lane & 15, four consecutive r) is already the operand layout of the
 //     up-projection; each wave contracts its quarter of the features, partials are summed through LDS in a fixed order.
 //   * The up-projection is computed as Y^T[c, tok]: every lane ends with 4 consecutive output columns of one token, the
-//     residual comes from the fragment registers kept from the down-projection (x is read from HBM once).
-//   * No store is issued before the last load: loads and stores share vmcnt and retire out of order with respect to
-//     each other, so a store in flight turns every later wait into vmcnt(0) = an HBM write round trip.
-// Adapter weights (72 KiB per matrix, bf16, fragment-major copies) are read through L1/L2.
+//     residual comes from the fragments the down-projection read (x is read from HBM once).
+//   * THE VMCNT RULE: no store is issued before the last load (of the kernel in form 1, of an iteration in forms 2 and 3):
+//     loads and stores share vmcnt and retire out of order with respect to each other, so a store in flight turns every
+//     later wait into vmcnt(0) = an HBM write round trip.
+// Adapter weights (72 KiB per matrix, bf16, fragment-major copies written by adapter_pack_kernel) are read through L1/L2 in
+// form 1 and once per block, into registers, in forms 2 and 3.
 // HBM-bound: 2 x T x 768 x 4 B algorithmic bytes per forward call (+ T x 768 x 2 B with the fused LayerNorm).
 #include <type_traits>
 
@@ -112,36 +130,30 @@ __device__ __forceinline__ bf16x8 pad8(const f32x4 a) {
     return bf16x8{(bf16)a[0], (bf16)a[1], (bf16)a[2], (bf16)a[3], 0, 0, 0, 0};
 }
 
-// K-split partial bottleneck tiles: wave w parks its partials at the start of its OWN staging region (its slice has
-// been consumed by then), slot s of NS at [s][lane] (f32x4); after the block barrier every wave sums the four regions
-// in a fixed order.
-template <int NS>
-__device__ __forceinline__ void ksplit_store(float* stg_all, int wave, int lane, int s, const f32x4 v) {
-    reinterpret_cast<f32x4*>(stg_all + wave * STG_WAVE)[s * 64 + lane] = v;
+// K-split partial bottleneck tiles: wave quarter w parks slot s at f32x4 [w * WSTRIDE + s * 64 + lane] of `base`; after the
+// block barrier every wave sums the four quarters in the fixed order w = 0..3.  Form 1: base = the staging regions, WSTRIDE =
+// one region (a wave's slice has been consumed by then); forms 2 and 3: the kspl area, [w][6 slots][64 lanes].
+template <int WSTRIDE>
+__device__ __forceinline__ void ksplit_store(float* base, int w, int lane, int s, const f32x4 v) {
+    reinterpret_cast<f32x4*>(base)[w * WSTRIDE + s * 64 + lane] = v;
 }
-template <int NS>
-__device__ __forceinline__ f32x4 ksplit_sum(const float* stg_all, int lane, int s) {
-    f32x4 t = reinterpret_cast<const f32x4*>(stg_all)[s * 64 + lane];
+template <int WSTRIDE>
+__device__ __forceinline__ f32x4 ksplit_sum(const float* base, int lane, int s) {
+    f32x4 t = reinterpret_cast<const f32x4*>(base)[s * 64 + lane];
 #pragma unroll
-    for (int w = 1; w < 4; ++w) t = t + reinterpret_cast<const f32x4*>(stg_all + w * STG_WAVE)[s * 64 + lane];
+    for (int w = 1; w < 4; ++w) t = t + reinterpret_cast<const f32x4*>(base)[w * WSTRIDE + s * 64 + lane];
     return t;
 }
 
-struct LnFuse {            // optional LayerNorm of the adapter output (the next layer's layernorm_before), fused
-    const float* gamma;    // null = off
-    const float* beta;
-    bf16* y16;             // [T, H] bf16: LN(out)
-    float* stats;          // [T, 2]: mean, rstd (for the LN backward)
-    float eps;
-};
-
-// ZS: the forward saved z = relu(Wd x + bd) for every adapter of the segment (feddat_adapter_fwd*'s z_save): the backward
-// then reads dy and 192-384 B of z per token instead of dy and x, and runs one K=768 product per adapter instead of two.
-template <int NA, bool ZS>
+// =====================================================================================================================
+// Form 1: one tile per block, z = relu(Wd x + bd) recomputed from x (the caller saved no z): reads dy and x, two K = 768
+// products per adapter.
+// =====================================================================================================================
+template <int NA>
 __device__ __forceinline__ void bwd_body(const float* __restrict__ x, const float* __restrict__ dy,
                                          float* __restrict__ dx, bf16* __restrict__ dx16, float* __restrict__ z_out,
                                          float* __restrict__ dz_out, const feddat_adapter_seg& sg, int row0,
-                                         float* stg_all, const float* __restrict__ z_saved) {
+                                         float* stg_all) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int g = lane >> 4, i16 = lane & 15;
     const int nvalid = (sg.row_end - row0) < 16 ? (sg.row_end - row0) : 16;
@@ -161,16 +173,7 @@ __device__ __forceinline__ void bwd_body(const float* __restrict__ x, const floa
         }
     f32x4 dyk[KS / 4][2];
     f32x4 vd[NLD];
-    if (ZS) {
-        // 1. the dy slice leaves HBM row-contiguous (12 x 16 B per lane in flight), next to it the saved z of the 16 tokens
-        slice_load(dy + (size_t)row0 * H + wave * WCOLS, nvalid, lane, vd);
-        const float* zrow = z_saved + (size_t)(valid ? row : row0 + nvalid - 1) * (2 * R) + 4 * g;
-#pragma unroll
-        for (int a = 0; a < NA; ++a)
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) z[a][nt] = *reinterpret_cast<const f32x4*>(zrow + a * R + nt * 16);
-        FD_COMPILER_FENCE();
-    } else {
+    {
         // 1. the x slice leaves HBM first (row-contiguous, 12 x 16 B per lane in flight); the dy slice is requested as
         // soon as x has been handed to LDS, so its latency hides behind the first down-projection
         f32x4 vx[NLD];
@@ -192,8 +195,8 @@ __device__ __forceinline__ void bwd_body(const float* __restrict__ x, const floa
     for (int a = 0; a < NA; ++a)
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) {
-            if (!ZS) ksplit_store<2 * NA * NT>(stg_all, wave, lane, a * NT + nt, z[a][nt]);
-            ksplit_store<2 * NA * NT>(stg_all, wave, lane, NA * NT + a * NT + nt, gr[a][nt]);
+            ksplit_store<STG_WAVE / 4>(stg_all, wave, lane, a * NT + nt, z[a][nt]);
+            ksplit_store<STG_WAVE / 4>(stg_all, wave, lane, NA * NT + a * NT + nt, gr[a][nt]);
         }
     __syncthreads();
 
@@ -206,16 +209,12 @@ __device__ __forceinline__ void bwd_body(const float* __restrict__ x, const floa
         const float sc = sg.scale[a];
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) {
-            const f32x4 gs = ksplit_sum<2 * NA * NT>(stg_all, lane, NA * NT + a * NT + nt);
+            const f32x4 gs = ksplit_sum<STG_WAVE / 4>(stg_all, lane, NA * NT + a * NT + nt);
+            const f32x4 zs = ksplit_sum<STG_WAVE / 4>(stg_all, lane, a * NT + nt);
+            const f32x4 b4 = *reinterpret_cast<const f32x4*>(sg.bd[a] + nt * 16 + 4 * g);
             f32x4 zz, dz;
-            if (ZS) {
-                zz = z[a][nt];
-            } else {
-                const f32x4 zs = ksplit_sum<2 * NA * NT>(stg_all, lane, a * NT + nt);
-                const f32x4 b4 = *reinterpret_cast<const f32x4*>(sg.bd[a] + nt * 16 + 4 * g);
 #pragma unroll
-                for (int e = 0; e < 4; ++e) zz[e] = fmaxf(zs[e] + b4[e], 0.f);
-            }
+            for (int e = 0; e < 4; ++e) zz[e] = fmaxf(zs[e] + b4[e], 0.f);
 #pragma unroll
             for (int e = 0; e < 4; ++e) dz[e] = zz[e] > 0.f ? sc * gs[e] : 0.f;
             gr[a][nt] = dz;
@@ -277,28 +276,29 @@ __device__ __forceinline__ void bwd_body(const float* __restrict__ x, const floa
     }
 }
 
-template <bool ZS>
 __global__ __launch_bounds__(256, 2) void adapter_bwd_kernel(const float* __restrict__ x, const float* __restrict__ dy,
                                                           float* __restrict__ dx, bf16* __restrict__ dx16,
                                                           float* __restrict__ z_out, float* __restrict__ dz_out,
-                                                          AdapterLaunch L, const float* __restrict__ z_saved) {
+                                                          AdapterLaunch L) {
     __shared__ __attribute__((aligned(16))) float stg[4 * STG_WAVE];
     const int tile = blockIdx.x;
     const int s = tile < L.tiles0 ? 0 : 1;
     const int t = s ? tile - L.tiles0 : tile;
     const feddat_adapter_seg& sg = L.seg[s];
     const int row0 = sg.row_begin + t * 16;
-    if (sg.n_adapters == 2) bwd_body<2, ZS>(x, dy, dx, dx16, z_out, dz_out, sg, row0, stg, z_saved);
-    else bwd_body<1, ZS>(x, dy, dx, dx16, z_out, dz_out, sg, row0, stg, z_saved);
+    if (sg.n_adapters == 2) bwd_body<2>(x, dy, dx, dx16, z_out, dz_out, sg, row0, stg);
+    else bwd_body<1>(x, dy, dx, dx16, z_out, dz_out, sg, row0, stg);
 }
 
 // =====================================================================================================================
-// Weight-stationary persistent forms, four waves per block (launched for the fp8 copy of dx and under debug flag
-// FD_DEBUG_ADAPTER_4W; every other launch takes the two-wave-group forms further down, which compute the same bits).
+// Streaming forms (2 and 3): weight-stationary persistent kernels.  The forward saves z = relu(Wd x + bd) of every adapter of
+// the segment (feddat_adapter_fwd*'s z_save); the backward then reads dy and 192-384 B of z per token instead of dy and x, and
+// runs one K = 768 product per adapter instead of two.  This section holds what the four-wave and the two-wave-group bodies
+// share; NW is the number of waves of the block (4 or 8), w4 = wave & 3 the quarter a wave works on.
 //
-// What bounded the one-tile-per-block kernels above (r02, PMC): 740 blocks in a single generation, each a serial chain
+// What bounded the one-tile-per-block kernels (r02, PMC): 740 blocks in a single generation, each a serial chain
 // load -> ~1 us of compute fed by 216-288 KB of weight fragments through L1/L2 -> store, with HBM idle during the compute
-// of all of them: 2.7 TB/s.  Here ONE block of 4 waves (one per SIMD, 512 registers each) stays on every CU:
+// of all of them: 2.7 TB/s.  Here ONE block (form 2: 4 waves, one per SIMD, 512 registers each) stays on every CU:
 //   * wave w keeps its quarter of every weight matrix of its segment IN REGISTERS for the whole launch: the K-quarter
 //     of the down-type matrix (6 k-steps x 3 r-tiles x 4 dwords = 72 per adapter) and the 12 column tiles of the up-type
 //     matrix (12 x 6 = 72 per adapter): 288 dwords per lane for the gated segment; after the prologue the compute phase
@@ -313,8 +313,17 @@ __global__ __launch_bounds__(256, 2) void adapter_bwd_kernel(const float* __rest
 // =====================================================================================================================
 constexpr int ROWT = H + 8;                   // floats per LDS tile row
 constexpr int TILE_F = 16 * ROWT;             // one 16-token tile: 49 664 B
-constexpr int KSPL_F = 4 * 6 * 64 * 4;        // K-split partials: 4 waves x 6 slots x 64 lanes x f32x4 = 24 KiB
+constexpr int KSPL_W = 6 * 64;                // K-split partials of one quarter: 6 slots (a * NT + nt) x 64 lanes (f32x4)
+constexpr int KSPL_F = 4 * KSPL_W * 4;        // ... of the four quarters: 24 KiB
 constexpr int ZT_F = 16 * 2 * R;              // saved-z tile of the backward: 6 KiB
+
+struct LnFuse {            // optional LayerNorm of the adapter output (the next layer's layernorm_before), fused
+    const float* gamma;    // null = off
+    const float* beta;
+    bf16* y16;             // [T, H] bf16: LN(out)
+    float* stats;          // [T, 2]: mean, rstd (for the LN backward)
+    float eps;
+};
 
 struct WsLaunch {
     AdapterLaunch a;
@@ -323,18 +332,50 @@ struct WsLaunch {
                    // 4 no DMA beyond the first tile -- timing only, results are wrong
 };
 
+// The dynamic LDS of a block, in floats from its base: two tile buffers and the K-split partials, then the forward's tables
+// or, in their place, the backward's saved-z tiles.  (Every pointer is the one base + a constant: keeps the accesses typed
+// as LDS, not flat.)  ws_bwd_body takes its three pointers from the constants instead of the struct: through the struct the
+// fp8 kernel's ISA moved.
+struct WsLds {
+    static constexpr int KSPL = 2 * TILE_F;                // [4 quarters][KSPL_W] f32x4
+    static constexpr int LNRED = KSPL + KSPL_F;            // forward: [4][16][2] (mean_w, M2_w), then [4][16][2] (mean, rstd)
+    static constexpr int SBU = LNRED + 256;                //   [2][H]  up-projection biases
+    static constexpr int SBD = SBU + 2 * H;                //   [2][64] down-projection biases
+    static constexpr int SGAM = SBD + 128;                 //   [H] gamma, [H] beta of the fused LayerNorm
+    static constexpr int SBET = SGAM + H;
+    static constexpr int FWD_F = SBET + H;
+    static constexpr int ZTILE = LNRED;                    // backward: [2][ZT_F]
+    static constexpr int AMRED = ZTILE + 2 * ZT_F;         //   [4 quarters][16 rows]: row maxima of |dx| (fp8 copy only)
+    static constexpr int BWD_F = AMRED + 64;
+    float *tile, *kspl, *lnred, *sbu, *sbd, *sgam, *sbet, *ztile, *amred;
+    __device__ __forceinline__ explicit WsLds(float* smem)
+        : tile(smem), kspl(smem + KSPL), lnred(smem + LNRED), sbu(smem + SBU), sbd(smem + SBD), sgam(smem + SGAM),
+          sbet(smem + SBET), ztile(smem + ZTILE), amred(smem + AMRED) {}
+};
+constexpr int WS_FWD_LDS = WsLds::FWD_F * 4, WS_BWD_LDS = WsLds::BWD_F * 4;
+static_assert(WS_FWD_LDS <= 160 * 1024 && WS_BWD_LDS <= 160 * 1024, "the CU has 160 KiB of LDS: no room for another buffer");
+
+// tile t of the segment: first row, valid rows
+struct TileRows {
+    int row0, nvalid;
+};
+__device__ __forceinline__ TileRows ws_tile_rows(const feddat_adapter_seg& sg, int t) {
+    const int row0 = sg.row_begin + t * 16;
+    return {row0, (sg.row_end - row0) < 16 ? (sg.row_end - row0) : 16};
+}
+
 #define FD_WAIT_VM0() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
 // After [tile 0 pieces][weight loads][tile 1 pieces] have been issued: tile 0 has landed once at most as many requests are
-// outstanding as were issued BEHIND it.  The count is derived from the loop bounds of ws_load_weights (one vector load per
-// fragment: NA x (NT*KS/4 down-type + CT/4 + 2*CT/8 up-type) = 42 per adapter) plus the 12 pieces of tile 1, capped at the
-// counter's 63; it is only valid when tile 1 exists -- a block with a single tile has just the weight loads behind tile 0 and
-// must wait for everything (ws_wait_tile0 below; block-uniform condition).
-constexpr int WS_WEIGHT_LOADS_PER_ADAPTER = NT * (KS / 4) + CT / 4 + 2 * (CT / 8);
-static_assert(WS_WEIGHT_LOADS_PER_ADAPTER == 42, "ws_load_weights changed: re-derive the counted wait");
-template <int NA>
+// outstanding as were issued BEHIND it by this wave: its WLOADS weight loads (one vector load per fragment: WsQuarter::LOADS,
+// from the loaders' loop bounds) plus its 48 / NW pieces of tile 1, capped at the counter's 63 (the gated four-wave segment
+// has 96 behind tile 0: everything older than the last 63 requests has landed).  The backward's saved-z piece of tile 1 is not
+// counted: the wait then covers one request more than it needs to.  The count is only valid when tile 1 exists -- a block
+// with a single tile has just the weight loads behind tile 0 and must wait for everything (block-uniform condition).
+template <int NW, int WLOADS>
 __device__ __forceinline__ void ws_wait_tile0(bool has_tile1) {
-    constexpr int behind = NA * WS_WEIGHT_LOADS_PER_ADAPTER + 12;
+    constexpr int behind = WLOADS + 48 / NW;
     constexpr int cnt = behind < 63 ? behind : 63;
+    static_assert(NW == 4 || behind <= 63, "the two-group waits are exact: re-derive them (vmcnt holds 63)");
     if (has_tile1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(cnt) : "memory");
     else FD_WAIT_VM0();
 }
@@ -347,42 +388,79 @@ __device__ __forceinline__ void ws_dma16(const float* g, const float* lds_dst) {
     const unsigned a = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)LDS_PTR(lds_dst));
     asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" : : "v"(g), "s"(a) : "memory");
 }
-// one 16-token tile, HBM -> LDS by DMA: 48 row pieces of 1 KiB, 12 per wave (wave w: rows 4w .. 4w+3)
+// one 16-token tile, HBM -> LDS by DMA: 48 row pieces of 1 KiB, 48 / NW per wave (wave w: rows (16 / NW) w ...)
+template <int NW>
 __device__ __forceinline__ void ws_tile_dma(const float* __restrict__ src, int nvalid, float* buf, int wave, int lane) {
 #pragma unroll
-    for (int j = 0; j < 12; ++j) {
-        const int r = wave * 4 + j / 3, part = j % 3;
+    for (int j = 0; j < 48 / NW; ++j) {
+        const int r = wave * (16 / NW) + j / 3, part = j % 3;
         const int rr = r < nvalid ? r : nvalid - 1;       // rows past the segment end re-read its last row
         ws_dma16(src + (size_t)rr * H + part * 256 + lane * 4, buf + r * ROWT + part * 256);
     }
 }
-__device__ __forceinline__ void ws_frags_from_lds(const float* buf, int wave, int lane, f32x4 (&keep)[KS / 4][2]) {
-    const float* p = buf + (lane & 15) * ROWT + wave * WCOLS + 4 * (lane >> 4);
-#pragma unroll
-    for (int k = 0; k < KS / 4; ++k) {
-        keep[k][0] = *reinterpret_cast<const f32x4*>(p + k * 32);
-        keep[k][1] = *reinterpret_cast<const f32x4*>(p + k * 32 + 16);
-    }
-}
-__device__ __forceinline__ void ws_frags_to_lds(float* buf, int wave, int lane, const f32x4 (&keep)[KS / 4][2]) {
-    float* p = buf + (lane & 15) * ROWT + wave * WCOLS + 4 * (lane >> 4);
-#pragma unroll
-    for (int k = 0; k < KS / 4; ++k) {
-        *reinterpret_cast<f32x4*>(p + k * 32) = keep[k][0];
-        *reinterpret_cast<f32x4*>(p + k * 32 + 16) = keep[k][1];
-    }
-}
 
-// register-resident weights of one wave: NA adapters x (K-quarter of the down-type matrix, 12 column tiles of the up-type one)
-template <int NA>
-struct WsWeights {
-    bf16x8 dn[NA][NT][KS / 4];
-    bf16x8 up01[NA][CT / 4];
-    bf16x8 up2[NA][CT / 8];      // r = 32..47 of column tiles 2p (slots 0-3) and 2p+1 (slots 4-7)
+// saved-z tile of the backward: 16 tokens x [2][48] fp32 = 6 KiB, contiguous in HBM -> 6 DMA pieces, one per wave 0..5 (of 4
+// waves: a second round for pieces 4 and 5).  The two arms of ws_ztile_dma say the same thing; each is the spelling under
+// which its kernels' ISA stays what it was (the loop alone moved adapter_bwd_g2_kernel, the straight form the four-wave ones).
+__device__ __forceinline__ void ws_zpiece_dma(const float* __restrict__ zs, int nvalid, float* dst, int piece, int lane) {
+    const int fo = piece * 256 + lane * 4, r = fo / (2 * R), c = fo - r * (2 * R);
+    const int rr = r < nvalid ? r : nvalid - 1;
+    ws_dma16(zs + (size_t)rr * (2 * R) + c, dst + piece * 256);
+}
+template <int NW>
+__device__ __forceinline__ void ws_ztile_dma(const float* __restrict__ zs, int nvalid, float* dst, int wave, int lane) {
+    if constexpr (NW == 8) {
+        if (wave < 6) ws_zpiece_dma(zs, nvalid, dst, wave, lane);
+    } else {
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+            if (wave + 4 * j < 6) ws_zpiece_dma(zs, nvalid, dst, wave + 4 * j, lane);
+    }
+}
+// Register-resident weights of one wave for ONE adapter: NTW r-tiles of the K-quarter of the down-type matrix, NK column
+// tiles of the up-type one.  A four-wave wave holds WsQuarter<NT, CT / 4> for every adapter of its segment; of two wave groups,
+// each wave holds that quarter of ONE adapter (gated segment) or WsQuarter<2, CT / 8>, its share of the single adapter.
+template <int NTW, int NK>
+struct WsQuarter {
+    static constexpr int LOADS = NTW * (KS / 4) + NK + 2 * (NK / 2);      // vector loads per wave (the loaders below)
+    bf16x8 dn[NTW][KS / 4];
+    bf16x8 up01[NK];
+    bf16x8 up2[NK / 2];          // r = 32..47 of column tiles 2p (slots 0-3) and 2p+1 (slots 4-7)
 };
+static_assert(WsQuarter<NT, CT / 4>::LOADS == 42 && WsQuarter<2, CT / 8>::LOADS == 24,
+              "the weight loaders changed: re-derive the counted waits");
+// The load ORDER (down-type, up01, up2) is part of the counted waits.  sgrp: the wave's group where two groups SPLIT one adapter
+// (0 everywhere else): group 1 takes r-tile NT - 1 in every r-tile slot (its second slot is loaded -- both groups issue the same
+// number of loads -- and never used) and the second NK column tiles of the quarter.
+template <int NTW, int NK>
+__device__ __forceinline__ void ws_load_quarter(WsQuarter<NTW, NK>& W, const void* dn, const void* up, int w4, int lane,
+                                                int sgrp) {
+    const bf16* d = (const bf16*)dn;
+    const bf16* u = (const bf16*)up;
+#pragma unroll
+    for (int i = 0; i < NTW; ++i) {
+        const int nt = sgrp ? NT - 1 : i;
+#pragma unroll
+        for (int k = 0; k < KS / 4; ++k)
+            W.dn[i][k] = *reinterpret_cast<const bf16x8*>(d + ((nt * KS + w4 * (KS / 4) + k) * 64 + lane) * 8);
+    }
+    const int ct0 = w4 * (CT / 4) + sgrp * NK;
+#pragma unroll
+    for (int k = 0; k < NK; ++k) W.up01[k] = *reinterpret_cast<const bf16x8*>(u + ((ct0 + k) * 64 + lane) * 8);
+#pragma unroll
+    for (int p = 0; p < NK / 2; ++p) {
+        const int ct = ct0 + 2 * p;
+        const bf16x4 lo = *reinterpret_cast<const bf16x4*>(u + CT * 64 * 8 + (ct * 64 + lane) * 4);
+        const bf16x4 hi = *reinterpret_cast<const bf16x4*>(u + CT * 64 * 8 + ((ct + 1) * 64 + lane) * 4);
+        W.up2[p] = bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+    }
+}
+// The four-wave bodies' loader: the whole quarters of all NA adapters of the segment, in the same order.  (Calling
+// ws_load_quarter once per adapter instead loads the same bytes but moved all three four-wave kernels' ISA, the production fp8
+// backward included.)
 template <int NA>
-__device__ __forceinline__ void ws_load_weights(WsWeights<NA>& W, const void* const* dn, const void* const* up, int wave,
-                                                int lane) {
+__device__ __forceinline__ void ws_load_quarters(WsQuarter<NT, CT / 4> (&W)[NA], const void* const* dn, const void* const* up,
+                                                 int wave, int lane) {
 #pragma unroll
     for (int a = 0; a < NA; ++a) {
         const bf16* d = (const bf16*)dn[a];
@@ -391,18 +469,18 @@ __device__ __forceinline__ void ws_load_weights(WsWeights<NA>& W, const void* co
         for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
             for (int k = 0; k < KS / 4; ++k)
-                W.dn[a][nt][k] = *reinterpret_cast<const bf16x8*>(d + ((nt * KS + wave * (KS / 4) + k) * 64 + lane) * 8);
+                W[a].dn[nt][k] = *reinterpret_cast<const bf16x8*>(d + ((nt * KS + wave * (KS / 4) + k) * 64 + lane) * 8);
 #pragma unroll
         for (int k = 0; k < CT / 4; ++k) {
             const int ct = wave * (CT / 4) + k;
-            W.up01[a][k] = *reinterpret_cast<const bf16x8*>(u + (ct * 64 + lane) * 8);
+            W[a].up01[k] = *reinterpret_cast<const bf16x8*>(u + (ct * 64 + lane) * 8);
         }
 #pragma unroll
         for (int p = 0; p < CT / 8; ++p) {
             const int ct = wave * (CT / 4) + 2 * p;
             const bf16x4 lo = *reinterpret_cast<const bf16x4*>(u + CT * 64 * 8 + (ct * 64 + lane) * 4);
             const bf16x4 hi = *reinterpret_cast<const bf16x4*>(u + CT * 64 * 8 + ((ct + 1) * 64 + lane) * 4);
-            W.up2[a][p] = bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+            W[a].up2[p] = bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
         }
     }
 }
@@ -410,6 +488,37 @@ __device__ __forceinline__ void ws_load_weights(WsWeights<NA>& W, const void* co
 // TWO column tiles: [z | 0] selects the even tile's weights (slots 0-3), [0 | z] the odd tile's (slots 4-7)
 __device__ __forceinline__ bf16x8 pad8hi(const f32x4 a) {
     return bf16x8{0, 0, 0, 0, (bf16)a[0], (bf16)a[1], (bf16)a[2], (bf16)a[3]};
+}
+
+// the two MFMAs of column tile k of an up-type product
+template <int NTW, int NK>
+__device__ __forceinline__ f32x4 ws_up_tile(const WsQuarter<NTW, NK>& W, int k, const bf16x8 b01, const bf16x8 (&b2)[2]) {
+    const f32x4 y = mfma16x32(W.up01[k], b01, f32x4{0.f, 0.f, 0.f, 0.f});
+    return mfma16x32(W.up2[k >> 1], b2[k & 1], y);
+}
+// forward prologue: biases of the segment's adapters and the LayerNorm's gamma / beta -> LDS
+template <int NA, int NW>
+__device__ __forceinline__ void ws_load_tables(const WsLds& lds, const feddat_adapter_seg& sg, const LnFuse& ln) {
+    for (int i = threadIdx.x; i < NA * H; i += 64 * NW) lds.sbu[i] = sg.bu[i / H][i % H];
+    if (threadIdx.x < NA * R) lds.sbd[(threadIdx.x / R) * 64 + threadIdx.x % R] = sg.bd[threadIdx.x / R][threadIdx.x % R];
+    if (ln.gamma)
+        for (int i = threadIdx.x; i < H; i += 64 * NW) {
+            lds.sgam[i] = ln.gamma[i];
+            lds.sbet[i] = ln.beta[i];
+        }
+}
+
+// The "DMA of tile t + 2" tail of an iteration: tile t of the block's walk, if it exists, into tile buffer `buf`: rows of src
+// (shifted by row_delta) and, in the backward (ZT), the saved z of the same tokens into zt.  (The prologues issue tiles 0 and 1
+// through a lambda of their own: through this function every kernel's ISA moved.)
+template <int NW, bool ZT>
+__device__ __forceinline__ void ws_fetch_tile(const float* __restrict__ src, int row_delta, const float* __restrict__ zs,
+                                              const feddat_adapter_seg& sg, int t, int ntiles, float* buf, float* zt, int wave,
+                                              int lane) {
+    if (t >= ntiles) return;
+    const TileRows tr = ws_tile_rows(sg, t);
+    ws_tile_dma<NW>(src + (size_t)(tr.row0 + row_delta) * H, tr.nvalid, buf, wave, lane);
+    if (ZT) ws_ztile_dma<NW>(zs + (size_t)tr.row0 * (2 * R), tr.nvalid, zt, wave, lane);
 }
 
 // block -> (segment, first tile, tile stride)
@@ -421,19 +530,18 @@ __device__ __forceinline__ void ws_walk(const WsLaunch& L, int& s, int& t0, int&
     const feddat_adapter_seg& sg = L.a.seg[s];
     ntiles = (sg.row_end - sg.row_begin + 15) / 16;
 }
+// (Every __global__ wrapper of the streaming kernels has the same shape: ws_walk, then if / else on the segment's n_adapters.)
 
+// =====================================================================================================================
+// Form 2, four waves per block, one per SIMD: wave = quarter, and every wave holds its quarter of EVERY adapter of the segment.
+// =====================================================================================================================
 template <int NA>
 __device__ __forceinline__ void ws_fwd_body(const float* __restrict__ x, float* __restrict__ out,
                                             const feddat_adapter_seg& sg, int t0, int tstep, int ntiles, float* smem,
                                             const LnFuse& ln, float* __restrict__ z_save, const int dbg) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int g = lane >> 4, i16 = lane & 15;
-    float* kspl = smem + 2 * TILE_F;
-    float* lnred = kspl + KSPL_F;              // 256 floats
-    float* sbu = lnred + 256;                  // [2][H]  up-projection biases
-    float* sbd = sbu + 2 * H;                  // [2][64] down-projection biases
-    float* sgam = sbd + 128;                   // [H] gamma, [H] beta of the fused LayerNorm
-    float* sbet = sgam + H;
+    const WsLds lds(smem);
     if (t0 >= ntiles) return;
 
     // ---- prologue: small tables -> LDS, then (in this order in the memory pipe) tile 0, the weights -> registers, tile 1.
@@ -445,26 +553,20 @@ __device__ __forceinline__ void ws_fwd_body(const float* __restrict__ x, float* 
     auto tile_dma = [&](int p) {
         const int t = t0 + p * tstep;
         if (t < ntiles && !(p && (dbg & 4))) {
-            const int row0 = sg.row_begin + t * 16;
-            const int nvalid = (sg.row_end - row0) < 16 ? (sg.row_end - row0) : 16;
-            ws_tile_dma(x + (size_t)(row0 + sg.x_row_delta) * H, nvalid, smem + p * TILE_F, wave, lane);
+            const TileRows tr = ws_tile_rows(sg, t);
+            const int row0 = tr.row0, nvalid = tr.nvalid;
+            ws_tile_dma<4>(x + (size_t)(row0 + sg.x_row_delta) * H, nvalid, lds.tile + p * TILE_F, wave, lane);
         }
     };
-    for (int i = threadIdx.x; i < NA * H; i += 256) sbu[i] = sg.bu[i / H][i % H];
-    if (threadIdx.x < NA * R) sbd[(threadIdx.x / R) * 64 + threadIdx.x % R] = sg.bd[threadIdx.x / R][threadIdx.x % R];
-    if (ln.gamma)
-        for (int i = threadIdx.x; i < H; i += 256) {
-            sgam[i] = ln.gamma[i];
-            sbet[i] = ln.beta[i];
-        }
+    ws_load_tables<NA, 4>(lds, sg, ln);
     float sc[NA];
 #pragma unroll
     for (int a = 0; a < NA; ++a) sc[a] = sg.scale[a];
     tile_dma(0);
-    WsWeights<NA> W;
-    ws_load_weights<NA>(W, sg.wd, sg.wu, wave, lane);
+    WsQuarter<NT, CT / 4> W[NA];
+    ws_load_quarters(W, sg.wd, sg.wu, wave, lane);
     tile_dma(1);
-    ws_wait_tile0<NA>(!(dbg & 4) && t0 + tstep < ntiles);
+    ws_wait_tile0<4, NA * WsQuarter<NT, CT / 4>::LOADS>(!(dbg & 4) && t0 + tstep < ntiles);
     __syncthreads();
 
     // Steady state, iteration t (its tile is in LDS): compute -> vmcnt(0) [tile t+1 landed; the stores of tile t-1, issued
@@ -472,9 +574,9 @@ __device__ __forceinline__ void ws_fwd_body(const float* __restrict__ x, float* 
     // The stores of tile t and the DMA of tile t+2 are in flight during the compute phase of tile t+1.
     int cur = 0;
     for (int t = t0; t < ntiles; t += tstep, cur ^= 1) {
-        const int row0 = sg.row_begin + t * 16;
-        const int nvalid = (sg.row_end - row0) < 16 ? (sg.row_end - row0) : 16;
-        float* buf = smem + cur * TILE_F;      // (one base pointer + offset: keeps the accesses typed as LDS, not flat)
+        const TileRows tr = ws_tile_rows(sg, t);
+        const int row0 = tr.row0, nvalid = tr.nvalid;
+        float* buf = lds.tile + cur * TILE_F;      // (one base pointer + offset: keeps the accesses typed as LDS, not flat)
 
         f32x4 z_keep[NA];
         float mean = 0.f, rstd = 0.f;
@@ -496,23 +598,20 @@ __device__ __forceinline__ void ws_fwd_body(const float* __restrict__ x, float* 
 #pragma unroll
             for (int a = 0; a < NA; ++a)
 #pragma unroll
-                for (int nt = 0; nt < NT; ++nt) z[a][nt] = mfma16x32(W.dn[a][nt][k], xf, z[a][nt]);
+                for (int nt = 0; nt < NT; ++nt) z[a][nt] = mfma16x32(W[a].dn[nt][k], xf, z[a][nt]);
         }
 #pragma unroll
         for (int a = 0; a < NA; ++a)
 #pragma unroll
-            for (int nt = 0; nt < NT; ++nt)
-                reinterpret_cast<f32x4*>(kspl)[(wave * 6 + a * NT + nt) * 64 + lane] = z[a][nt];
+            for (int nt = 0; nt < NT; ++nt) ksplit_store<KSPL_W>(lds.kspl, wave, lane, a * NT + nt, z[a][nt]);
         __syncthreads();
         bf16x8 zb01[NA], zb2[NA][2];
 #pragma unroll
         for (int a = 0; a < NA; ++a) {
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) {
-                f32x4 tsum = reinterpret_cast<const f32x4*>(kspl)[(a * NT + nt) * 64 + lane];
-#pragma unroll
-                for (int w = 1; w < 4; ++w) tsum = tsum + reinterpret_cast<const f32x4*>(kspl)[(w * 6 + a * NT + nt) * 64 + lane];
-                const f32x4 b4 = *reinterpret_cast<const f32x4*>(sbd + a * 64 + nt * 16 + 4 * g);
+                const f32x4 tsum = ksplit_sum<KSPL_W>(lds.kspl, lane, a * NT + nt);
+                const f32x4 b4 = *reinterpret_cast<const f32x4*>(lds.sbd + a * 64 + nt * 16 + 4 * g);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) z[a][nt][e] = fmaxf(tsum[e] + b4[e], 0.f);
                 if (nt == wave) z_keep[a] = z[a][nt];      // wave nt stores r-tile nt (with the other stores, below)
@@ -530,9 +629,8 @@ __device__ __forceinline__ void ws_fwd_body(const float* __restrict__ x, float* 
             f32x4 o = *reinterpret_cast<const f32x4*>(frag + k * 16);
 #pragma unroll
             for (int a = 0; a < NA; ++a) {
-                f32x4 y = mfma16x32(W.up01[a][k], zb01[a], f32x4{0.f, 0.f, 0.f, 0.f});
-                y = mfma16x32(W.up2[a][k >> 1], zb2[a][k & 1], y);
-                const f32x4 bu4 = *reinterpret_cast<const f32x4*>(sbu + a * H + c);
+                const f32x4 y = ws_up_tile(W[a], k, zb01[a], zb2[a]);
+                const f32x4 bu4 = *reinterpret_cast<const f32x4*>(lds.sbu + a * H + c);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) o[e] += sc[a] * (y[e] + bu4[e]);
             }
@@ -563,24 +661,31 @@ __device__ __forceinline__ void ws_fwd_body(const float* __restrict__ x, float* 
             s2 += __shfl_xor(s2, 16, 64);
             s2 += __shfl_xor(s2, 32, 64);
             if (g == 0) {
-                lnred[wave * 32 + 2 * i16] = mw;
-                lnred[wave * 32 + 2 * i16 + 1] = s2;
+                lds.lnred[wave * 32 + 2 * i16] = mw;
+                lds.lnred[wave * 32 + 2 * i16 + 1] = s2;
             }
             __syncthreads();
-            const float m0 = lnred[2 * i16], m1 = lnred[32 + 2 * i16], m2 = lnred[64 + 2 * i16], m3 = lnred[96 + 2 * i16];
+            const float m0 = lds.lnred[2 * i16], m1 = lds.lnred[32 + 2 * i16], m2 = lds.lnred[64 + 2 * i16], m3 = lds.lnred[96 + 2 * i16];
             mean = ((m0 + m1) + (m2 + m3)) * 0.25f;
             const float q0 = m0 - mean, q1 = m1 - mean, q2 = m2 - mean, q3 = m3 - mean;
-            const float M2 = ((lnred[2 * i16 + 1] + lnred[32 + 2 * i16 + 1]) + (lnred[64 + 2 * i16 + 1] + lnred[96 + 2 * i16 + 1])) +
+            const float M2 = ((lds.lnred[2 * i16 + 1] + lds.lnred[32 + 2 * i16 + 1]) + (lds.lnred[64 + 2 * i16 + 1] + lds.lnred[96 + 2 * i16 + 1])) +
                              (float)WCOLS * ((q0 * q0 + q1 * q1) + (q2 * q2 + q3 * q3));
             rstd = rsqrtf(M2 * (1.0f / H) + ln.eps);
             if (g == 0) {
-                lnred[128 + wave * 32 + 2 * i16] = mean;
-                lnred[128 + wave * 32 + 2 * i16 + 1] = rstd;
+                lds.lnred[128 + wave * 32 + 2 * i16] = mean;
+                lds.lnred[128 + wave * 32 + 2 * i16 + 1] = rstd;
             }
         }
 
         // 5. outputs: fragment layout -> LDS (this wave's own columns of the tile buffer) -> row-contiguous stores
-        ws_frags_to_lds(buf, wave, lane, xk);
+        {
+            float* p = buf + i16 * ROWT + wave * WCOLS + 4 * g;
+#pragma unroll
+            for (int k = 0; k < KS / 4; ++k) {
+                *reinterpret_cast<f32x4*>(p + k * 32) = xk[k][0];
+                *reinterpret_cast<f32x4*>(p + k * 32 + 16) = xk[k][1];
+            }
+        }
         }
         float* orow = out + (size_t)row0 * H + wave * WCOLS;
         const float* srow = buf + wave * WCOLS;
@@ -611,9 +716,9 @@ __device__ __forceinline__ void ws_fwd_body(const float* __restrict__ x, float* 
 #pragma unroll
                 for (int j = 0; j < NLD; ++j) {
                     const int r = 4 * (j / 3) + g, c = 16 * (j % 3) + i16;
-                    const float m = lnred[128 + wave * 32 + 2 * r], rs = lnred[128 + wave * 32 + 2 * r + 1];
-                    const f32x4 gm = *reinterpret_cast<const f32x4*>(sgam + wave * WCOLS + c * 4);
-                    const f32x4 bt = *reinterpret_cast<const f32x4*>(sbet + wave * WCOLS + c * 4);
+                    const float m = lds.lnred[128 + wave * 32 + 2 * r], rs = lds.lnred[128 + wave * 32 + 2 * r + 1];
+                    const f32x4 gm = *reinterpret_cast<const f32x4*>(lds.sgam + wave * WCOLS + c * 4);
+                    const f32x4 bt = *reinterpret_cast<const f32x4*>(lds.sbet + wave * WCOLS + c * 4);
                     f32x4 y;
 #pragma unroll
                     for (int e = 0; e < 4; ++e) y[e] = (v[j][e] - m) * rs * gm[e] + bt[e];
@@ -630,15 +735,9 @@ __device__ __forceinline__ void ws_fwd_body(const float* __restrict__ x, float* 
             else emit(std::false_type{});
         }
         __syncthreads();                       // every wave: next tile visible, this buffer consumed
-        if (t + 2 * tstep < ntiles && !(dbg & 4)) {
-            const int rn = sg.row_begin + (t + 2 * tstep) * 16;
-            const int nv = (sg.row_end - rn) < 16 ? (sg.row_end - rn) : 16;
-            ws_tile_dma(x + (size_t)(rn + sg.x_row_delta) * H, nv, buf, wave, lane);
-        }
+        if (!(dbg & 4)) ws_fetch_tile<4, false>(x, sg.x_row_delta, nullptr, sg, t + 2 * tstep, ntiles, buf, nullptr, wave, lane);
     }
 }
-
-constexpr int WS_FWD_LDS = (2 * TILE_F + KSPL_F + 256 + 2 * H + 128 + 2 * H) * 4;
 
 __global__ __launch_bounds__(256, 1) void adapter_fwd_ws_kernel(const float* __restrict__ x, float* __restrict__ out,
                                                                 WsLaunch L, LnFuse ln, float* __restrict__ z_save) {
@@ -651,19 +750,6 @@ __global__ __launch_bounds__(256, 1) void adapter_fwd_ws_kernel(const float* __r
 }
 
 
-// saved-z tile of the backward: 16 tokens x [2][48] fp32 = 6 KiB, contiguous in HBM -> 6 DMA pieces
-__device__ __forceinline__ void ws_ztile_dma(const float* __restrict__ zs, int nvalid, float* dst, int wave, int lane) {
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int piece = wave + 4 * j;
-        if (piece < 6) {
-            const int fo = piece * 256 + lane * 4, r = fo / (2 * R), c = fo - r * (2 * R);
-            const int rr = r < nvalid ? r : nvalid - 1;
-            ws_dma16(zs + (size_t)rr * (2 * R) + c, dst + piece * 256);
-        }
-    }
-}
-
 // Backward, z saved by the forward.  Register-resident: WuT (down-type: g = Wu^T dy) and WdT (up-type: dx = dy + Wd^T dz).
 // Q8 (configs[4] only, its own instantiation so that the default kernel's register plan is untouched): dx also as e4m3 rows.
 template <int NA, bool Q8>
@@ -674,48 +760,49 @@ __device__ __forceinline__ void ws_bwd_body(const float* __restrict__ dy, float*
                                             unsigned char* __restrict__ dx8, float* __restrict__ dx8_scale) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int g = lane >> 4, i16 = lane & 15;
-    float* kspl = smem + 2 * TILE_F;
-    float* ztile = kspl + KSPL_F;              // [2][ZT_F]
-    float* amred = ztile + 2 * ZT_F;           // [4 waves][16 rows]: row maxima of |dx| (fp8 copy only)
+    float* kspl = smem + WsLds::KSPL;
+    float* ztile = smem + WsLds::ZTILE;
+    float* amred = smem + WsLds::AMRED;
     if (t0 >= ntiles) return;
     auto tile_dma = [&](int p) {       // prologue order and waits as in ws_fwd_body
         const int t = t0 + p * tstep;
         if (t < ntiles && !(p && (dbg & 4))) {
-            const int row0 = sg.row_begin + t * 16;
-            const int nvalid = (sg.row_end - row0) < 16 ? (sg.row_end - row0) : 16;
-            ws_tile_dma(dy + (size_t)row0 * H, nvalid, smem + p * TILE_F, wave, lane);
-            ws_ztile_dma(z_saved + (size_t)row0 * (2 * R), nvalid, ztile + p * ZT_F, wave, lane);
+            const TileRows tr = ws_tile_rows(sg, t);
+            const int row0 = tr.row0, nvalid = tr.nvalid;
+            ws_tile_dma<4>(dy + (size_t)row0 * H, nvalid, smem + p * TILE_F, wave, lane);
+            ws_ztile_dma<4>(z_saved + (size_t)row0 * (2 * R), nvalid, ztile + p * ZT_F, wave, lane);
         }
     };
-    if (Q8) {      // (the fp8 instantiation keeps the one-wait prologue: any other form costs it 7 spilled registers)
+    if (Q8) {      // (the fp8 instantiation keeps the one-wait prologue: any other form costs it 7 spilled registers; the loop
+                   // repeats tile_dma's text because tile_dma(0), tile_dma(1) in its place moves this kernel's ISA)
 #pragma unroll
         for (int p = 0; p < 2; ++p) {
             const int t = t0 + p * tstep;
             if (t < ntiles && !(p && (dbg & 4))) {
-                const int row0 = sg.row_begin + t * 16;
-                const int nvalid = (sg.row_end - row0) < 16 ? (sg.row_end - row0) : 16;
-                ws_tile_dma(dy + (size_t)row0 * H, nvalid, smem + p * TILE_F, wave, lane);
-                ws_ztile_dma(z_saved + (size_t)row0 * (2 * R), nvalid, ztile + p * ZT_F, wave, lane);
+                const TileRows tr = ws_tile_rows(sg, t);
+                const int row0 = tr.row0, nvalid = tr.nvalid;
+                ws_tile_dma<4>(dy + (size_t)row0 * H, nvalid, smem + p * TILE_F, wave, lane);
+                ws_ztile_dma<4>(z_saved + (size_t)row0 * (2 * R), nvalid, ztile + p * ZT_F, wave, lane);
             }
         }
     } else {
         tile_dma(0);
     }
-    WsWeights<NA> W;
-    ws_load_weights<NA>(W, sg.wuT, sg.wdT, wave, lane);
+    WsQuarter<NT, CT / 4> W[NA];
+    ws_load_quarters(W, sg.wuT, sg.wdT, wave, lane);
     if (!Q8) tile_dma(1);
     float sc[NA];
 #pragma unroll
     for (int a = 0; a < NA; ++a) sc[a] = sg.scale[a];
     const int train_slot = sg.train_slot;
     const bool exp_z = train_slot >= 0 && wave < NT && z_out;
-    ws_wait_tile0<NA>(!Q8 && !(dbg & 4) && t0 + tstep < ntiles);
+    ws_wait_tile0<4, NA * WsQuarter<NT, CT / 4>::LOADS>(!Q8 && !(dbg & 4) && t0 + tstep < ntiles);
     __syncthreads();
 
     int cur = 0;      // pipeline order as in ws_fwd_body
     for (int t = t0; t < ntiles; t += tstep, cur ^= 1) {
-        const int row0 = sg.row_begin + t * 16;
-        const int nvalid = (sg.row_end - row0) < 16 ? (sg.row_end - row0) : 16;
+        const TileRows tr = ws_tile_rows(sg, t);
+        const int row0 = tr.row0, nvalid = tr.nvalid;
         float* buf = smem + cur * TILE_F;
         float* zt = ztile + cur * ZT_F;
 
@@ -735,13 +822,12 @@ __device__ __forceinline__ void ws_bwd_body(const float* __restrict__ dy, float*
 #pragma unroll
             for (int a = 0; a < NA; ++a)
 #pragma unroll
-                for (int nt = 0; nt < NT; ++nt) gr[a][nt] = mfma16x32(W.dn[a][nt][k], df, gr[a][nt]);
+                for (int nt = 0; nt < NT; ++nt) gr[a][nt] = mfma16x32(W[a].dn[nt][k], df, gr[a][nt]);
         }
 #pragma unroll
         for (int a = 0; a < NA; ++a)
 #pragma unroll
-            for (int nt = 0; nt < NT; ++nt)
-                reinterpret_cast<f32x4*>(kspl)[(wave * 6 + a * NT + nt) * 64 + lane] = gr[a][nt];
+            for (int nt = 0; nt < NT; ++nt) ksplit_store<KSPL_W>(kspl, wave, lane, a * NT + nt, gr[a][nt]);
         __syncthreads();
 
         // dz = scale * g * (z > 0); z and dz of the trainable slot go out for the weight gradients
@@ -774,8 +860,7 @@ __device__ __forceinline__ void ws_bwd_body(const float* __restrict__ dy, float*
                 f32x4 o = *reinterpret_cast<const f32x4*>(frag + k * 16);
 #pragma unroll
                 for (int a = 0; a < NA; ++a) {
-                    f32x4 y = mfma16x32(W.up01[a][k], dzb01[a], f32x4{0.f, 0.f, 0.f, 0.f});
-                    y = mfma16x32(W.up2[a][k >> 1], dzb2[a][k & 1], y);
+                    const f32x4 y = ws_up_tile(W[a], k, dzb01[a], dzb2[a]);
                     o = o + y;
                 }
                 *reinterpret_cast<f32x4*>(buf + i16 * ROWT + wave * WCOLS + 4 * g + k * 16) = o;
@@ -862,16 +947,9 @@ __device__ __forceinline__ void ws_bwd_body(const float* __restrict__ dy, float*
             else emit(std::false_type{});
         }
         __syncthreads();                       // every wave: next tile visible, this buffer consumed
-        if (t + 2 * tstep < ntiles && !(dbg & 4)) {
-            const int rn = sg.row_begin + (t + 2 * tstep) * 16;
-            const int nv = (sg.row_end - rn) < 16 ? (sg.row_end - rn) : 16;
-            ws_tile_dma(dy + (size_t)rn * H, nv, buf, wave, lane);
-            ws_ztile_dma(z_saved + (size_t)rn * (2 * R), nv, zt, wave, lane);
-        }
+        if (!(dbg & 4)) ws_fetch_tile<4, true>(dy, 0, z_saved, sg, t + 2 * tstep, ntiles, buf, zt, wave, lane);
     }
 }
-
-constexpr int WS_BWD_LDS = (2 * TILE_F + KSPL_F + 2 * ZT_F + 64) * 4;
 
 template <bool Q8>
 __global__ __launch_bounds__(256, 1) void adapter_bwd_ws_kernel(const float* __restrict__ dy, float* __restrict__ dx,
@@ -889,8 +967,8 @@ __global__ __launch_bounds__(256, 1) void adapter_bwd_ws_kernel(const float* __r
 }
 
 // =====================================================================================================================
-// Two wave groups per block: the forms the entry points launch (debug flag FD_DEBUG_ADAPTER_4W selects the four-wave
-// kernels above instead; the results are bit-identical).
+// Form 3, two wave groups per block: the kernels the entry points launch (debug flag FD_DEBUG_ADAPTER_4W selects the
+// four-wave kernels above instead; the results are bit-identical).
 //
 // What bounded the four-wave kernels (tools/adapter_ablate.py): with one wave per SIMD the compute phase of a tile
 // is ONE dependent chain per SIMD -- LDS fragment reads, MFMA latencies, two block exchanges -- and nothing else can issue
@@ -915,99 +993,20 @@ __global__ __launch_bounds__(256, 1) void adapter_bwd_ws_kernel(const float* __r
 // The vmcnt rule of the file header holds: no store is issued before the last load of an iteration.
 // =====================================================================================================================
 constexpr int G2_THREADS = 512;
-static_assert(WS_FWD_LDS <= 160 * 1024 && WS_BWD_LDS <= 160 * 1024, "the CU has 160 KiB of LDS: no room for another buffer");
-
+// the weights of one wave: its adapter's quarter (gated segment) or its share of the single adapter's quarter, where group 1
+// uses one of its two r-tile slots
 template <int NA>
-struct G2Weights {
-    static constexpr int NTW = NA == 2 ? NT : 2;             // r-tiles of the down-type matrix (single: group 1 uses one)
-    static constexpr int NK = NA == 2 ? CT / 4 : CT / 8;     // column tiles of the up-type matrix
-    static constexpr int LOADS = NTW * (KS / 4) + NK + 2 * (NK / 2);      // vector loads per wave (g2_load_weights)
-    bf16x8 dn[NTW][KS / 4];
-    bf16x8 up01[NK];
-    bf16x8 up2[NK / 2];          // r = 32..47 of column tiles 2p (slots 0-3) and 2p+1 (slots 4-7)
-};
-static_assert(G2Weights<2>::LOADS == 42 && G2Weights<1>::LOADS == 24, "g2_load_weights changed: re-derive the counted wait");
-
-template <int NA>
-__device__ __forceinline__ void g2_load_weights(G2Weights<NA>& W, const void* dn, const void* up, int grp, int w4, int lane) {
-    constexpr int NTW = G2Weights<NA>::NTW, NK = G2Weights<NA>::NK;
-    const bf16* d = (const bf16*)dn;
-    const bf16* u = (const bf16*)up;
-#pragma unroll
-    for (int i = 0; i < NTW; ++i) {
-        // single: group 1's second slot repeats r-tile 2 -- loaded (both groups issue the same number of loads: the counted
-        // wait), never used
-        const int nt = NA == 2 ? i : (grp ? NT - 1 : i);
-#pragma unroll
-        for (int k = 0; k < KS / 4; ++k)
-            W.dn[i][k] = *reinterpret_cast<const bf16x8*>(d + ((nt * KS + w4 * (KS / 4) + k) * 64 + lane) * 8);
-    }
-    const int ct0 = w4 * (CT / 4) + (NA == 2 ? 0 : grp * NK);
-#pragma unroll
-    for (int k = 0; k < NK; ++k) W.up01[k] = *reinterpret_cast<const bf16x8*>(u + ((ct0 + k) * 64 + lane) * 8);
-#pragma unroll
-    for (int p = 0; p < NK / 2; ++p) {
-        const int ct = ct0 + 2 * p;
-        const bf16x4 lo = *reinterpret_cast<const bf16x4*>(u + CT * 64 * 8 + (ct * 64 + lane) * 4);
-        const bf16x4 hi = *reinterpret_cast<const bf16x4*>(u + CT * 64 * 8 + ((ct + 1) * 64 + lane) * 4);
-        W.up2[p] = bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    }
-}
-// As ws_wait_tile0, for 8 waves: behind a wave's pieces of tile 0 come its weight loads (42 for one adapter of the gated
-// segment, 24 for its share of the single adapter) and its 6 pieces of tile 1 (the backward's saved-z piece of tile 1 is
-// not counted: the wait then covers one request more than it needs to).
-template <int NA>
-__device__ __forceinline__ void g2_wait_tile0(bool has_tile1) {
-    constexpr int behind = G2Weights<NA>::LOADS + 6;
-    static_assert(behind == (NA == 2 ? 48 : 30) && behind <= 63, "re-derive the counted wait (vmcnt holds 63)");
-    if (has_tile1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(behind) : "memory");
-    else FD_WAIT_VM0();
-}
-// one 16-token tile, HBM -> LDS by DMA: 48 row pieces of 1 KiB, 6 per wave (wave W: rows 2W, 2W+1)
-__device__ __forceinline__ void g2_tile_dma(const float* __restrict__ src, int nvalid, float* buf, int wave, int lane) {
-#pragma unroll
-    for (int j = 0; j < 6; ++j) {
-        const int r = wave * 2 + j / 3, part = j % 3;
-        const int rr = r < nvalid ? r : nvalid - 1;       // rows past the segment end re-read its last row
-        ws_dma16(src + (size_t)rr * H + part * 256 + lane * 4, buf + r * ROWT + part * 256);
-    }
-}
-// saved-z tile of the backward: 6 DMA pieces, waves 0..5
-__device__ __forceinline__ void g2_ztile_dma(const float* __restrict__ zs, int nvalid, float* dst, int wave, int lane) {
-    if (wave < 6) {
-        const int fo = wave * 256 + lane * 4, r = fo / (2 * R), c = fo - r * (2 * R);
-        const int rr = r < nvalid ? r : nvalid - 1;
-        ws_dma16(zs + (size_t)rr * (2 * R) + c, dst + wave * 256);
-    }
-}
-// the two MFMAs of one column tile of an up-type product
-template <int NA>
-__device__ __forceinline__ f32x4 g2_up_tile(const G2Weights<NA>& W, int k, const bf16x8 b01, const bf16x8 (&b2)[2]) {
-    const f32x4 y = mfma16x32(W.up01[k], b01, f32x4{0.f, 0.f, 0.f, 0.f});
-    return mfma16x32(W.up2[k >> 1], b2[k & 1], y);
-}
-// K-split sum of slot s in the fixed order w = 0..3 (the four-wave layout of kspl: [w][6 slots][64 lanes])
-__device__ __forceinline__ f32x4 g2_ksum(const float* kspl, int s, int lane) {
-    f32x4 t = reinterpret_cast<const f32x4*>(kspl)[s * 64 + lane];
-#pragma unroll
-    for (int w = 1; w < 4; ++w) t = t + reinterpret_cast<const f32x4*>(kspl)[(w * 6 + s) * 64 + lane];
-    return t;
-}
+using G2Weights = WsQuarter<NA == 2 ? NT : 2, NA == 2 ? CT / 4 : CT / 8>;
 
 template <int NA>
 __device__ __forceinline__ void g2_fwd_body(const float* __restrict__ x, float* __restrict__ out,
                                             const feddat_adapter_seg& sg, int t0, int tstep, int ntiles, float* smem,
                                             const LnFuse& ln, float* __restrict__ z_save, const int dbg) {
 #pragma clang fp contract(off)
-    constexpr int NTW = G2Weights<NA>::NTW, NK = G2Weights<NA>::NK;
+    constexpr int NTW = NA == 2 ? NT : 2, NK = NA == 2 ? CT / 4 : CT / 8;
     const int lane0 = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), grp = wave >> 2, w4 = wave & 3;
-    float* kspl = smem + 2 * TILE_F;
-    float* lnred = kspl + KSPL_F;              // 256 floats
-    float* sbu = lnred + 256;                  // [2][H]  up-projection biases
-    float* sbd = sbu + 2 * H;                  // [2][64] down-projection biases
-    float* sgam = sbd + 128;                   // [H] gamma, [H] beta of the fused LayerNorm
-    float* sbet = sgam + H;
+    const WsLds lds(smem);
     if (t0 >= ntiles) return;                  // block-uniform: no group leaves alone
     const int ad = NA == 2 ? grp : 0;          // this wave's adapter
     const int ntc = NA == 2 ? NT : (grp ? 1 : 2);        // r-tiles this wave contracts: nt0 .. nt0 + ntc - 1
@@ -1020,32 +1019,26 @@ __device__ __forceinline__ void g2_fwd_body(const float* __restrict__ x, float* 
     auto tile_dma = [&](int p) {
         const int t = t0 + p * tstep;
         if (t < ntiles && !(p && (dbg & 4))) {
-            const int row0 = sg.row_begin + t * 16;
-            const int nvalid = (sg.row_end - row0) < 16 ? (sg.row_end - row0) : 16;
-            g2_tile_dma(x + (size_t)(row0 + sg.x_row_delta) * H, nvalid, smem + p * TILE_F, wave, lane0);
+            const TileRows tr = ws_tile_rows(sg, t);
+            const int row0 = tr.row0, nvalid = tr.nvalid;
+            ws_tile_dma<8>(x + (size_t)(row0 + sg.x_row_delta) * H, nvalid, lds.tile + p * TILE_F, wave, lane0);
         }
     };
-    for (int i = threadIdx.x; i < NA * H; i += G2_THREADS) sbu[i] = sg.bu[i / H][i % H];
-    if (threadIdx.x < NA * R) sbd[(threadIdx.x / R) * 64 + threadIdx.x % R] = sg.bd[threadIdx.x / R][threadIdx.x % R];
-    if (ln.gamma)
-        for (int i = threadIdx.x; i < H; i += G2_THREADS) {
-            sgam[i] = ln.gamma[i];
-            sbet[i] = ln.beta[i];
-        }
+    ws_load_tables<NA, 8>(lds, sg, ln);
     const float sc0 = sg.scale[0], sc1 = sg.scale[NA - 1];
     tile_dma(0);
     G2Weights<NA> W;
-    g2_load_weights<NA>(W, ad ? sg.wd[NA - 1] : sg.wd[0], ad ? sg.wu[NA - 1] : sg.wu[0], grp, w4, lane0);
+    ws_load_quarter(W, ad ? sg.wd[NA - 1] : sg.wd[0], ad ? sg.wu[NA - 1] : sg.wu[0], w4, lane0, NA == 2 ? 0 : grp);
     tile_dma(1);
-    g2_wait_tile0<NA>(!(dbg & 4) && t0 + tstep < ntiles);
+    ws_wait_tile0<8, G2Weights<NA>::LOADS>(!(dbg & 4) && t0 + tstep < ntiles);
     __syncthreads();
 
     // Steady state as in ws_fwd_body: compute -> vmcnt(0) -> stores of tile t -> barrier -> DMA of tile t+2.
     int cur = 0;
     for (int t = t0; t < ntiles; t += tstep, cur ^= 1) {
-        const int row0 = sg.row_begin + t * 16;
-        const int nvalid = (sg.row_end - row0) < 16 ? (sg.row_end - row0) : 16;
-        float* buf = smem + cur * TILE_F;
+        const TileRows tr = ws_tile_rows(sg, t);
+        const int row0 = tr.row0, nvalid = tr.nvalid;
+        float* buf = lds.tile + cur * TILE_F;
         // lane-derived LDS and global offsets are re-derived per tile from a laundered lane id: hoisted out of the loop they
         // cost more registers than the 256 a wave has next to its 144 weight dwords
         int lane = lane0;
@@ -1082,15 +1075,15 @@ __device__ __forceinline__ void g2_fwd_body(const float* __restrict__ x, float* 
         }
 #pragma unroll
         for (int i = 0; i < NTW; ++i)
-            if (NA == 2 || i < ntc) reinterpret_cast<f32x4*>(kspl)[(w4 * 6 + slot0 + nt0 + i) * 64 + lane] = z[i];
+            if (NA == 2 || i < ntc) reinterpret_cast<f32x4*>(lds.kspl)[(w4 * 6 + slot0 + nt0 + i) * 64 + lane] = z[i];
         __syncthreads();
 
         // 2. K-split sums of this wave's adapter, bias, ReLU (every wave: all three r-tiles)
         f32x4 zz[NT];
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) {
-            const f32x4 tsum = g2_ksum(kspl, slot0 + nt, lane);
-            const f32x4 b4 = *reinterpret_cast<const f32x4*>(sbd + ad * 64 + nt * 16 + 4 * g);
+            const f32x4 tsum = ksplit_sum<KSPL_W>(lds.kspl, lane, slot0 + nt);
+            const f32x4 b4 = *reinterpret_cast<const f32x4*>(lds.sbd + ad * 64 + nt * 16 + 4 * g);
 #pragma unroll
             for (int e = 0; e < 4; ++e) zz[nt][e] = fmaxf(tsum[e] + b4[e], 0.f);
             if (nt == w4) z_keep = zz[nt];         // quarter nt stores r-tile nt (with the other stores, below)
@@ -1106,12 +1099,12 @@ __device__ __forceinline__ void g2_fwd_body(const float* __restrict__ x, float* 
             // holds the finished tiles for the LayerNorm sums.  (The products are common code of both groups: as two arms of a
             // branch their 48 result registers are allocated twice.)
 #pragma unroll
-            for (int k = 0; k < CT / 4; ++k) xk[k] = g2_up_tile<NA>(W, k, zb01, zb2);
+            for (int k = 0; k < CT / 4; ++k) xk[k] = ws_up_tile(W, k, zb01, zb2);
             if (!grp) {
 #pragma unroll
                 for (int k = 0; k < CT / 4; ++k) {
                     f32x4 o = *reinterpret_cast<const f32x4*>(frag + k * 16);
-                    const f32x4 bu4 = *reinterpret_cast<const f32x4*>(sbu + (w4 * (CT / 4) + k) * 16 + 4 * g);
+                    const f32x4 bu4 = *reinterpret_cast<const f32x4*>(lds.sbu + (w4 * (CT / 4) + k) * 16 + 4 * g);
 #pragma unroll
                     for (int e = 0; e < 4; ++e) o[e] = __builtin_fmaf(sc0, xk[k][e] + bu4[e], o[e]);
                     *reinterpret_cast<f32x4*>(frag + k * 16) = o;
@@ -1122,7 +1115,7 @@ __device__ __forceinline__ void g2_fwd_body(const float* __restrict__ x, float* 
 #pragma unroll
                 for (int k = 0; k < CT / 4; ++k) {
                     f32x4 o = *reinterpret_cast<const f32x4*>(frag + k * 16);
-                    const f32x4 bu4 = *reinterpret_cast<const f32x4*>(sbu + H + (w4 * (CT / 4) + k) * 16 + 4 * g);
+                    const f32x4 bu4 = *reinterpret_cast<const f32x4*>(lds.sbu + H + (w4 * (CT / 4) + k) * 16 + 4 * g);
 #pragma unroll
                     for (int e = 0; e < 4; ++e) o[e] = __builtin_fmaf(sc1, xk[k][e] + bu4[e], o[e]);
                     xk[k] = o;
@@ -1135,8 +1128,8 @@ __device__ __forceinline__ void g2_fwd_body(const float* __restrict__ x, float* 
 #pragma unroll
             for (int i = 0; i < NK; ++i) {
                 f32x4 o = *reinterpret_cast<const f32x4*>(frag + (kb + i) * 16);
-                const f32x4 y = g2_up_tile<NA>(W, i, zb01, zb2);
-                const f32x4 bu4 = *reinterpret_cast<const f32x4*>(sbu + (w4 * (CT / 4) + kb + i) * 16 + 4 * g);
+                const f32x4 y = ws_up_tile(W, i, zb01, zb2);
+                const f32x4 bu4 = *reinterpret_cast<const f32x4*>(lds.sbu + (w4 * (CT / 4) + kb + i) * 16 + 4 * g);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) o[e] = __builtin_fmaf(sc0, y[e] + bu4[e], o[e]);
                 xk[i] = o;
@@ -1174,24 +1167,24 @@ __device__ __forceinline__ void g2_fwd_body(const float* __restrict__ x, float* 
                 s2 += __shfl_xor(s2, 16, 64);
                 s2 += __shfl_xor(s2, 32, 64);
                 if (g == 0) {
-                    lnred[w4 * 32 + 2 * i16] = mw;
-                    lnred[w4 * 32 + 2 * i16 + 1] = s2;
+                    lds.lnred[w4 * 32 + 2 * i16] = mw;
+                    lds.lnred[w4 * 32 + 2 * i16 + 1] = s2;
                 }
             }
             __syncthreads();
             if (grp == lg) {
-                const float m0 = lnred[2 * i16], m1 = lnred[32 + 2 * i16], m2 = lnred[64 + 2 * i16], m3 = lnred[96 + 2 * i16];
+                const float m0 = lds.lnred[2 * i16], m1 = lds.lnred[32 + 2 * i16], m2 = lds.lnred[64 + 2 * i16], m3 = lds.lnred[96 + 2 * i16];
                 const float ms = (m0 + m1) + (m2 + m3);
                 mean = ms * 0.25f;
                 const float q0 = __builtin_fmaf(ms, -0.25f, m0), q1 = __builtin_fmaf(ms, -0.25f, m1),
                             q2 = __builtin_fmaf(ms, -0.25f, m2), q3 = __builtin_fmaf(ms, -0.25f, m3);
                 const float M2 = __builtin_fmaf((float)WCOLS, (q0 * q0 + q1 * q1) + (q2 * q2 + q3 * q3),
-                                                (lnred[2 * i16 + 1] + lnred[32 + 2 * i16 + 1]) +
-                                                    (lnred[64 + 2 * i16 + 1] + lnred[96 + 2 * i16 + 1]));
+                                                (lds.lnred[2 * i16 + 1] + lds.lnred[32 + 2 * i16 + 1]) +
+                                                    (lds.lnred[64 + 2 * i16 + 1] + lds.lnred[96 + 2 * i16 + 1]));
                 rstd = rsqrtf(__builtin_fmaf(M2, 1.0f / H, ln.eps));
                 if (g == 0) {
-                    lnred[128 + w4 * 32 + 2 * i16] = mean;
-                    lnred[128 + w4 * 32 + 2 * i16 + 1] = rstd;
+                    lds.lnred[128 + w4 * 32 + 2 * i16] = mean;
+                    lds.lnred[128 + w4 * 32 + 2 * i16 + 1] = rstd;
                 }
             }
         }
@@ -1226,9 +1219,9 @@ __device__ __forceinline__ void g2_fwd_body(const float* __restrict__ x, float* 
 #pragma unroll
                 for (int j = 0; j < NLG; ++j) {
                     const int r = 8 * grp + 4 * (j / 3) + g, c = 16 * (j % 3) + i16;
-                    const float m = lnred[128 + w4 * 32 + 2 * r], rs = lnred[128 + w4 * 32 + 2 * r + 1];
-                    const f32x4 gm = *reinterpret_cast<const f32x4*>(sgam + w4 * WCOLS + c * 4);
-                    const f32x4 bt = *reinterpret_cast<const f32x4*>(sbet + w4 * WCOLS + c * 4);
+                    const float m = lds.lnred[128 + w4 * 32 + 2 * r], rs = lds.lnred[128 + w4 * 32 + 2 * r + 1];
+                    const f32x4 gm = *reinterpret_cast<const f32x4*>(lds.sgam + w4 * WCOLS + c * 4);
+                    const f32x4 bt = *reinterpret_cast<const f32x4*>(lds.sbet + w4 * WCOLS + c * 4);
                     f32x4 y;
 #pragma unroll
                     for (int e = 0; e < 4; ++e) y[e] = __builtin_fmaf((v[j][e] - m) * rs, gm[e], bt[e]);
@@ -1245,11 +1238,7 @@ __device__ __forceinline__ void g2_fwd_body(const float* __restrict__ x, float* 
             else emit(std::false_type{});
         }
         __syncthreads();                       // every wave: next tile visible, this buffer consumed
-        if (t + 2 * tstep < ntiles && !(dbg & 4)) {
-            const int rn = sg.row_begin + (t + 2 * tstep) * 16;
-            const int nv = (sg.row_end - rn) < 16 ? (sg.row_end - rn) : 16;
-            g2_tile_dma(x + (size_t)(rn + sg.x_row_delta) * H, nv, buf, wave, lane);
-        }
+        if (!(dbg & 4)) ws_fetch_tile<8, false>(x, sg.x_row_delta, nullptr, sg, t + 2 * tstep, ntiles, buf, nullptr, wave, lane);
     }
 }
 
@@ -1272,11 +1261,10 @@ __device__ __forceinline__ void g2_bwd_body(const float* __restrict__ dy, float*
                                             const feddat_adapter_seg& sg, int t0, int tstep, int ntiles, float* smem,
                                             const float* __restrict__ z_saved, const int dbg) {
 #pragma clang fp contract(off)
-    constexpr int NTW = G2Weights<NA>::NTW, NK = G2Weights<NA>::NK;
+    constexpr int NTW = NA == 2 ? NT : 2, NK = NA == 2 ? CT / 4 : CT / 8;
     const int lane0 = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), grp = wave >> 2, w4 = wave & 3;
-    float* kspl = smem + 2 * TILE_F;
-    float* ztile = kspl + KSPL_F;              // [2][ZT_F]
+    const WsLds lds(smem);
     if (t0 >= ntiles) return;                  // block-uniform
     const int ad = NA == 2 ? grp : 0;
     const int ntc = NA == 2 ? NT : (grp ? 1 : 2);
@@ -1286,33 +1274,33 @@ __device__ __forceinline__ void g2_bwd_body(const float* __restrict__ dy, float*
     auto tile_dma = [&](int p) {       // prologue order and waits as in g2_fwd_body
         const int t = t0 + p * tstep;
         if (t < ntiles && !(p && (dbg & 4))) {
-            const int row0 = sg.row_begin + t * 16;
-            const int nvalid = (sg.row_end - row0) < 16 ? (sg.row_end - row0) : 16;
-            g2_tile_dma(dy + (size_t)row0 * H, nvalid, smem + p * TILE_F, wave, lane0);
-            g2_ztile_dma(z_saved + (size_t)row0 * (2 * R), nvalid, ztile + p * ZT_F, wave, lane0);
+            const TileRows tr = ws_tile_rows(sg, t);
+            const int row0 = tr.row0, nvalid = tr.nvalid;
+            ws_tile_dma<8>(dy + (size_t)row0 * H, nvalid, lds.tile + p * TILE_F, wave, lane0);
+            ws_ztile_dma<8>(z_saved + (size_t)row0 * (2 * R), nvalid, lds.ztile + p * ZT_F, wave, lane0);
         }
     };
     tile_dma(0);
     G2Weights<NA> W;
-    g2_load_weights<NA>(W, ad ? sg.wuT[NA - 1] : sg.wuT[0], ad ? sg.wdT[NA - 1] : sg.wdT[0], grp, w4, lane0);
+    ws_load_quarter(W, ad ? sg.wuT[NA - 1] : sg.wuT[0], ad ? sg.wdT[NA - 1] : sg.wdT[0], w4, lane0, NA == 2 ? 0 : grp);
     tile_dma(1);
     const float sca = ad ? sg.scale[NA - 1] : sg.scale[0];
     const int train_slot = sg.train_slot;
     const bool exp_z = train_slot == ad && (NA == 2 || !grp) && w4 < NT && z_out;   // the trainable slot's group exports z, dz
-    g2_wait_tile0<NA>(!(dbg & 4) && t0 + tstep < ntiles);
+    ws_wait_tile0<8, G2Weights<NA>::LOADS>(!(dbg & 4) && t0 + tstep < ntiles);
     __syncthreads();
 
     int cur = 0;      // pipeline order as in ws_fwd_body
     for (int t = t0; t < ntiles; t += tstep, cur ^= 1) {
-        const int row0 = sg.row_begin + t * 16;
-        const int nvalid = (sg.row_end - row0) < 16 ? (sg.row_end - row0) : 16;
-        float* buf = smem + cur * TILE_F;
+        const TileRows tr = ws_tile_rows(sg, t);
+        const int row0 = tr.row0, nvalid = tr.nvalid;
+        float* buf = lds.tile + cur * TILE_F;
         // lane-derived LDS and global offsets are re-derived per tile from a laundered lane id: hoisted out of the loop they
         // cost more registers than the 256 a wave has next to its 144 weight dwords
         int lane = lane0;
         asm volatile("" : "+v"(lane));
         const int g = lane >> 4, i16 = lane & 15;
-        float* zt = ztile + cur * ZT_F;
+        float* zt = lds.ztile + cur * ZT_F;
 
         f32x4 z_keep = f32x4{0.f, 0.f, 0.f, 0.f}, dz_keep = z_keep;
         if (!(dbg & 2)) {
@@ -1342,14 +1330,14 @@ __device__ __forceinline__ void g2_bwd_body(const float* __restrict__ dy, float*
         }
 #pragma unroll
         for (int i = 0; i < NTW; ++i)
-            if (NA == 2 || i < ntc) reinterpret_cast<f32x4*>(kspl)[(w4 * 6 + slot0 + nt0 + i) * 64 + lane] = gr[i];
+            if (NA == 2 || i < ntc) reinterpret_cast<f32x4*>(lds.kspl)[(w4 * 6 + slot0 + nt0 + i) * 64 + lane] = gr[i];
         __syncthreads();
 
         // dz = scale * g * (z > 0); z and dz of the trainable slot go out for the weight gradients
         f32x4 dzv[NT];
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) {
-            const f32x4 gs = g2_ksum(kspl, slot0 + nt, lane);
+            const f32x4 gs = ksplit_sum<KSPL_W>(lds.kspl, lane, slot0 + nt);
             const f32x4 zz = *reinterpret_cast<const f32x4*>(zt + i16 * (2 * R) + ad * R + nt * 16 + 4 * g);
             f32x4 dz;
 #pragma unroll
@@ -1369,7 +1357,7 @@ __device__ __forceinline__ void g2_bwd_body(const float* __restrict__ dy, float*
                 // (the products are common code of both groups: as two arms of a branch the 48 result registers are allocated twice)
                 f32x4 y[CT / 4];
 #pragma unroll
-                for (int k = 0; k < CT / 4; ++k) y[k] = g2_up_tile<NA>(W, k, dzb01, dzb2);
+                for (int k = 0; k < CT / 4; ++k) y[k] = ws_up_tile(W, k, dzb01, dzb2);
                 if (!grp) {
 #pragma unroll
                     for (int k = 0; k < CT / 4; ++k) {
@@ -1388,7 +1376,7 @@ __device__ __forceinline__ void g2_bwd_body(const float* __restrict__ dy, float*
             } else {
 #pragma unroll
                 for (int i = 0; i < NK; ++i) {
-                    const f32x4 o = *reinterpret_cast<const f32x4*>(frag + (kb + i) * 16) + g2_up_tile<NA>(W, i, dzb01, dzb2);
+                    const f32x4 o = *reinterpret_cast<const f32x4*>(frag + (kb + i) * 16) + ws_up_tile(W, i, dzb01, dzb2);
                     *reinterpret_cast<f32x4*>(frag + (kb + i) * 16) = o;
                 }
             }
@@ -1435,12 +1423,7 @@ __device__ __forceinline__ void g2_bwd_body(const float* __restrict__ dy, float*
             else emit(std::false_type{});
         }
         __syncthreads();                       // every wave: next tile visible, this buffer consumed
-        if (t + 2 * tstep < ntiles && !(dbg & 4)) {
-            const int rn = sg.row_begin + (t + 2 * tstep) * 16;
-            const int nv = (sg.row_end - rn) < 16 ? (sg.row_end - rn) : 16;
-            g2_tile_dma(dy + (size_t)rn * H, nv, buf, wave, lane);
-            g2_ztile_dma(z_saved + (size_t)rn * (2 * R), nv, zt, wave, lane);
-        }
+        if (!(dbg & 4)) ws_fetch_tile<8, true>(dy, 0, z_saved, sg, t + 2 * tstep, ntiles, buf, zt, wave, lane);
     }
 }
 
@@ -1454,6 +1437,15 @@ __global__ __launch_bounds__(G2_THREADS, 1) void adapter_bwd_g2_kernel(const flo
     const feddat_adapter_seg& sg = L.a.seg[s];
     if (sg.n_adapters == 2) g2_bwd_body<2>(dy, dx, dx16, z_out, dz_out, sg, t0, tstep, ntiles, ws_smem, z_saved, FD_ABL(L.dbg));
     else g2_bwd_body<1>(dy, dx, dx16, z_out, dz_out, sg, t0, tstep, ntiles, ws_smem, z_saved, FD_ABL(L.dbg));
+}
+
+// host: one launch of a streaming kernel on its plan
+template <class... KA>
+int ws_launch(void (*kern)(KA...), int grid, int threads, int lds, hipStream_t stream, std::common_type_t<KA>... args) {
+    const int rc = fd_set_max_lds((const void*)kern, lds);
+    if (rc) return rc;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, stream, args...);
+    FD_LAUNCH_RET();
 }
 
 // host: blocks per segment, proportional to the tiles (at least one block per non-empty segment, one block per CU in all).
@@ -1554,18 +1546,11 @@ int ws_launch_fwd(const float* x, float* out, const AdapterLaunch& A, int tiles,
                   hipStream_t stream) {
     WsLaunch W;
     int grid;
-    int rc = ws_plan(A, tiles, W, grid);
+    const int rc = ws_plan(A, tiles, W, grid);
     if (rc) return rc;
-    if (fd_debug_flags() & FD_DEBUG_ADAPTER_4W) {       // A/B: the four-wave kernel (bit-identical)
-        rc = fd_set_max_lds((const void*)adapter_fwd_ws_kernel, WS_FWD_LDS);
-        if (rc) return rc;
-        hipLaunchKernelGGL(adapter_fwd_ws_kernel, dim3(grid), dim3(256), WS_FWD_LDS, stream, x, out, W, ln, z_save);
-        FD_LAUNCH_RET();
-    }
-    rc = fd_set_max_lds((const void*)adapter_fwd_g2_kernel, WS_FWD_LDS);
-    if (rc) return rc;
-    hipLaunchKernelGGL(adapter_fwd_g2_kernel, dim3(grid), dim3(G2_THREADS), WS_FWD_LDS, stream, x, out, W, ln, z_save);
-    FD_LAUNCH_RET();
+    if (fd_debug_flags() & FD_DEBUG_ADAPTER_4W)        // A/B: the four-wave kernel (bit-identical)
+        return ws_launch(adapter_fwd_ws_kernel, grid, 256, WS_FWD_LDS, stream, x, out, W, ln, z_save);
+    return ws_launch(adapter_fwd_g2_kernel, grid, G2_THREADS, WS_FWD_LDS, stream, x, out, W, ln, z_save);
 }
 
 }  // namespace
@@ -1604,32 +1589,23 @@ static int adapter_bwd_launch(const float* x, const float* z_saved, const float*
     const int rc = prep_launch(segs, nseg, T, L, tiles, true);
     if (rc) return rc;
     if (tiles == 0) return FEDDAT_OK;
-    if (z_saved) {
-        WsLaunch W;
-        int grid;
-        const int rc2 = ws_plan(L, tiles, W, grid);
-        if (rc2) return rc2;
-        if (dx_fp8) {
-            const int rc3 = fd_set_max_lds((const void*)adapter_bwd_ws_kernel<true>, WS_BWD_LDS);
-            if (rc3) return rc3;
-            hipLaunchKernelGGL(adapter_bwd_ws_kernel<true>, dim3(grid), dim3(256), WS_BWD_LDS, stream, dy, dx, (bf16*)dx_bf16,
-                               z_out, dz_out, W, z_saved, (unsigned char*)dx_fp8, dx_scale);
-        } else if (fd_debug_flags() & FD_DEBUG_ADAPTER_4W) {       // A/B: the four-wave kernel (bit-identical)
-            const int rc3 = fd_set_max_lds((const void*)adapter_bwd_ws_kernel<false>, WS_BWD_LDS);
-            if (rc3) return rc3;
-            hipLaunchKernelGGL(adapter_bwd_ws_kernel<false>, dim3(grid), dim3(256), WS_BWD_LDS, stream, dy, dx, (bf16*)dx_bf16,
-                               z_out, dz_out, W, z_saved, (unsigned char*)nullptr, (float*)nullptr);
-        } else {
-            const int rc3 = fd_set_max_lds((const void*)adapter_bwd_g2_kernel, WS_BWD_LDS);
-            if (rc3) return rc3;
-            hipLaunchKernelGGL(adapter_bwd_g2_kernel, dim3(grid), dim3(G2_THREADS), WS_BWD_LDS, stream, dy, dx, (bf16*)dx_bf16,
-                               z_out, dz_out, W, z_saved);
-        }
-    } else {
-        hipLaunchKernelGGL(adapter_bwd_kernel<false>, dim3(tiles), dim3(256), dbg_extra_lds(), stream, x, dy, dx,
-                           (bf16*)dx_bf16, z_out, dz_out, L, z_saved);
+    if (!z_saved) {      // no saved z: recompute it from x, one tile per block
+        hipLaunchKernelGGL(adapter_bwd_kernel, dim3(tiles), dim3(256), dbg_extra_lds(), stream, x, dy, dx, (bf16*)dx_bf16, z_out,
+                           dz_out, L);
+        FD_LAUNCH_RET();
     }
-    FD_LAUNCH_RET();
+    WsLaunch W;
+    int grid;
+    const int rc2 = ws_plan(L, tiles, W, grid);
+    if (rc2) return rc2;
+    if (dx_fp8)
+        return ws_launch(adapter_bwd_ws_kernel<true>, grid, 256, WS_BWD_LDS, stream, dy, dx, (bf16*)dx_bf16, z_out, dz_out, W,
+                         z_saved, (unsigned char*)dx_fp8, dx_scale);
+    if (fd_debug_flags() & FD_DEBUG_ADAPTER_4W)         // A/B: the four-wave kernel (bit-identical)
+        return ws_launch(adapter_bwd_ws_kernel<false>, grid, 256, WS_BWD_LDS, stream, dy, dx, (bf16*)dx_bf16, z_out, dz_out, W,
+                         z_saved, nullptr, nullptr);
+    return ws_launch(adapter_bwd_g2_kernel, grid, G2_THREADS, WS_BWD_LDS, stream, dy, dx, (bf16*)dx_bf16, z_out, dz_out, W,
+                     z_saved);
 }
 
 extern "C" int feddat_adapter_bwd(const float* x, const float* z_saved, const float* dy, float* dx, void* dx_bf16,
