@@ -8,10 +8,17 @@ the adapters of vit.py:99-110 (after the MLP residual) and xbert.py:438-445 / ad
 before and after the adapter).  As in the ViLT engine, no arithmetic happens in Python / PyTorch: torch owns device
 buffers and the stream, every launch goes through the C ABI.
 
-Step algebra: only adapter tensors are trainable (main.py:138-159: the LM head `.cls.` is personal but frozen), so the
-no-grad gated pass P0 and the gated pass P2 of one train_step are the same computation (P1 updates adapter_1 only, the
-gated passes read adapter_0 / adapter_2) -> the gated forward runs ONCE; its logits serve as the teacher of P1 and as the
-student of P2.  Nothing trainable lies below the first ViT block's adapter, so the backward stops there.
+Step algebra.  The reference trains the adapters (main.py:138-159) AND the decoder's LM head: prepare_model ends by making every
+parameter whose name contains `.cls.` trainable (main.py:247-250 -- text_decoder.cls.predictions.{bias, transform.dense.weight,
+transform.dense.bias, transform.LayerNorm.weight, transform.LayerNorm.bias}; the tied decoder.weight is listed under the word
+embeddings and stays frozen), and `.cls.` is personal (main.py:127-128): per client, never averaged.  Here that is the opt-in
+`train_lm_head=True`; the DEFAULT (False) still keeps the head frozen, which is what the fixtures G10 - G12 were captured with.
+With the head frozen the no-grad gated pass P0 and the gated pass P2 of one train_step are the same computation (P1 updates
+adapter_1 only, the gated passes read adapter_0 / adapter_2) -> the gated forward runs ONCE; its logits serve as the teacher of
+P1 and as the student of P2.  With the head trainable the towers of P0 and P2 are still the same computation, but P1's optimizer
+step moves the head between them (create_optimizer takes every requires_grad parameter, so the head is stepped in BOTH sub-steps:
+task_trainer.py:302-308,323-328): the gated decoder output is kept and only the LM head runs again on it with the updated
+tensors (_step_kernels_head).  Nothing trainable lies below the first ViT block's adapter, so the backward stops there.
 
 Dropout.  The reference trains under model.train() (task_trainer.py:75) with hidden_dropout_prob =
 attention_probs_dropout_prob = 0.1 (src/configs/model_configs.py:44-46) in the two BERT towers -- after the embedding
@@ -59,14 +66,29 @@ def slab_question_of_row(ks: Sequence[int], N: int) -> List[int]:
     return q + [q[-1]] * (N - len(q))
 
 
+LM_HEAD = PRE + "text_decoder.cls.predictions."
+
+
+def lm_head_group_spec(vocab: int, H: int = 768):
+    """(names and shapes, padding) of the flat group that holds the trainable LM head: the five tensors main.py:247-250 makes
+    trainable on ALBEF (622 650 floats at a vocabulary of 30 522), transform.dense.weight first (16-byte aligned for the refresh
+    kernel), the vocabulary bias last and followed by the padding of the vocabulary axis to a multiple of 128.  Weight decay
+    follows the names (local_update._no_decay): transform.dense.weight alone is decayed."""
+    spec = [(LM_HEAD + "transform.dense.weight", (H, H)), (LM_HEAD + "transform.dense.bias", (H,)),
+            (LM_HEAD + "transform.LayerNorm.weight", (H,)), (LM_HEAD + "transform.LayerNorm.bias", (H,)),
+            (LM_HEAD + "bias", (vocab,))]
+    return spec, (vocab + 127) // 128 * 128 - vocab
+
+
 class AlbefDatEngine(LocalUpdateEngine):
     def __init__(self, params: Dict[str, torch.Tensor], device, batch: int, n_answers: int, q_len: int = 25, a_len: int = 4,
                  vit_depth: int = 12, enc_layers: int = 12, fusion_layer: int = 6, dec_layers: int = 6, image: int = 384,
                  vocab: int = 30522, lr: float = 1e-4, weight_decay: float = 1e-2, adam_eps: float = 1e-8, pad_id: int = 0,
                  max_pos: int = 512, dropout: float = 0.0, seed: int = 0, stack_text: bool = False,
                  operands: str = "f16", loss_scale: Optional[float] = None, dynamic_loss_scale: Optional[bool] = None,
-                 scale_growth_interval: int = 2000):
-        """operands="f16": every 16-bit MFMA operand in IEEE half (libfeddat_hip_f16.so) with a power-of-two loss scale on
+                 scale_growth_interval: int = 2000, train_lm_head: bool = False):
+        """train_lm_head: train text_decoder.cls.predictions.* as the reference does (module docstring); off by default.
+        operands="f16": every 16-bit MFMA operand in IEEE half (libfeddat_hip_f16.so) with a power-of-two loss scale on
         dL/dlogits (feddat_lm_loss_fwd_bwd's grad_scale, default 2^14) that leaves through feddat_wgrad_seg.grad_unscale -- the
         ViLT engine's scheme (engine.ViltDatEngine), with the same device-side dynamic scaler (dynamic_loss_scale, default on for
         "f16").  The default operand format is fp16 -- in this class, in train.main (--encoder_name albef_no_distill without
@@ -76,9 +98,11 @@ class AlbefDatEngine(LocalUpdateEngine):
         operands at 7.6e-4 / 8.4e-4 (0.024 / 0.028): both inside north_star's 1e-3, bf16 with a fifth of it to spare, for 1.5 % of
         the step (tests/test_sizes_gpu.py::test_albef_full_size_round_of_40_steps_vs_reference_golden asserts all four)."""
         # fp16 operands: the loss scale is dynamic by default -- LocalUpdateEngine's GradScaler on the device, as in ViltDatEngine
-        # (DESIGN.md section 5b).  The LM head is frozen here, so the two sub-steps share no trainable tensor: flag B (adapter_0's
+        # (DESIGN.md section 5b).  With the LM head frozen the two sub-steps share no trainable tensor: flag B (adapter_0's
         # pass) skips adapter_0's step alone; flag A (adapter_1's pass) voids the batch like in the ViLT engine (one finish kernel).
+        # A trainable head is shared by the two sub-steps exactly like the ViLT task head: _dat_tail's restore / skip predicates.
         self._init_loss_scale(operands, loss_scale, dynamic_loss_scale, scale_growth_interval)
+        self.train_lm_head = bool(train_lm_head)
         with L.operands(operands):
             self._init(params, device, batch, n_answers, q_len, a_len, vit_depth, enc_layers, fusion_layer, dec_layers, image, vocab,
                        lr, weight_decay, adam_eps, pad_id, max_pos, dropout, seed, stack_text)
@@ -180,6 +204,29 @@ class AlbefDatEngine(LocalUpdateEngine):
         self.head = dict(t=lin(c + "transform.dense"), lng=Pm(c + "transform.LayerNorm.weight"),
                          lnb=Pm(c + "transform.LayerNorm.bias"), w=bf16_of(wemb), wT=bf16_T(wemb), b=bpad)
         del wemb
+        self.lm = None
+        if self.train_lm_head:
+            # the five trainable head tensors in one flat fp32 group (AdamW state; weight decay on transform.dense.weight alone:
+            # local_update._no_decay).  The vocabulary bias comes last, followed by the Vp - V floats of vocabulary padding, so that
+            # its gradient -- the column sums of the [R, Vp] dlogits -- is reduced at the padded width.  The kernels read the fp32
+            # vectors (dense bias, LayerNorm gamma / beta) straight from the group; W, W^T and the padded bias are operand copies
+            # that feddat_lm_head_refresh rewrites after every head update.
+            c_ = PRE + c
+            spec, pad = lm_head_group_spec(vocab, H)
+            self.lm = FlatGroup(spec, dev, with_opt=True, pad=pad)
+            for n in self.lm.names:
+                self.lm.view(n).copy_(params[n].to(dev, torch.float32))
+            self.head["t"]["b"] = self.lm.view(c_ + "transform.dense.bias")
+            self.head["lng"] = self.lm.view(c_ + "transform.LayerNorm.weight")
+            self.head["lnb"] = self.lm.view(c_ + "transform.LayerNorm.bias")
+            # the tied decoder weight a second time: the 16-bit REMAINDER of its 16-bit copy (W_emb - fp32(operand(W_emb)), frozen,
+            # formed once here).  dy = dlogits W_emb is dominated by the rows of the label tokens, so the operand rounding of those
+            # embedding rows goes straight into the head's gradients; a second product with the remainder removes it.
+            wemb = torch.zeros(self.Vp, H, device=dev)
+            wemb[:vocab] = self.dec["word"]
+            self.head["wT_lo"] = bf16_T(wemb - self.head["w"].float())
+            del wemb
+            self._refresh_head()
 
         # ---------------- trainable state: three adapters over the 30 modules, flat per adapter ----------------
         self.modules: List[str] = [f"visual_encoder.blocks.{i}.adapter." for i in range(vit_depth)] + \
@@ -225,6 +272,8 @@ class AlbefDatEngine(LocalUpdateEngine):
         self._alloc()
         if self.dropout > 0:       # teacher logits of P0: the gated text pass is re-run (other masks) for P2
             self.logits_all = torch.empty(self.R, self.Vp, device=dev)
+        if self.train_lm_head:
+            self._alloc_head_grads()
 
     # ------------------------------------------------------------------------------------------ buffers
     def _alloc(self):
@@ -659,13 +708,64 @@ class AlbefDatEngine(LocalUpdateEngine):
         out, _ = self._bert_fwd(self.dec, D, self.vd + self.el, mode, t["Ma"], t["na"], La, t["amask8"], True, S["enc_rep16"], Lq,
                                 Lq, t["qmask8_rep"], pass_id, 1)
         # BertOnlyMLMHead on the positions that predict a next token (logits[:, :-1])
-        hd = self.head
         L.gather_rows(out, t["sel_idx"], dst_f32=S["hsel"], dst_bf16=S["hsel16"])
-        L.gemm_bf16_nt(S["hsel16"], hd["t"]["w"], L.EPI_F32, bias=hd["t"]["b"], out_f32=S["tu"])
-        L.gelu_fwd(S["tu"], S["tg"])
-        L.layernorm_fwd(S["tg"], hd["lng"], hd["lnb"], 1e-12, t["R"], H, y_bf16=S["ty16"], stats=S["tst"])
-        L.gemm_bf16_nt(S["ty16"], hd["w"], L.EPI_F32, bias=hd["b"], out_f32=S["logits"])
+        self._lm_head_fwd(S, 0, t["R"])
         return S["logits"]
+
+    def _lm_head_fwd(self, S, lo: int, hi: int):
+        """BertOnlyMLMHead (transform.dense, gelu, transform.LayerNorm, tied decoder + bias) on rows [lo, hi) of the selected
+        decoder states S["hsel16"], with the head as it stands.  A train_step with a trainable head calls it a second time on the
+        gated rows, after sub-step A's head update: the towers below did not change."""
+        hd, H = self.head, self.H
+        if self.train_lm_head:
+            # transform.dense in fp32 from the group's master weight (fp32 MFMA, rows x 768 x 768: small): tu, gelu(tu) and the
+            # LayerNorm statistics feed the head's own gradients
+            key = ("head-dense", S["hsel"].data_ptr(), lo, hi)
+            if key not in self._segs_cache:
+                w32 = self.lm.view(self.lm.names[0])          # out[i, j] = sum_k x[i, k] W[j, k] + b[j]
+                self._segs_cache[key] = L.ht_job(S["hsel"][lo:hi], H, 1, w32, 1, H, hi - lo, H, H, S["tu"][lo:hi], bias_j=hd["t"]["b"])
+            L.head_gemm(self._segs_cache[key])
+        else:
+            L.gemm_bf16_nt(S["hsel16"][lo:hi], hd["t"]["w"], L.EPI_F32, bias=hd["t"]["b"], out_f32=S["tu"][lo:hi])
+        L.gelu_fwd(S["tu"][lo:hi], S["tg"][lo:hi])
+        L.layernorm_fwd(S["tg"][lo:hi], hd["lng"], hd["lnb"], 1e-12, hi - lo, H, y_bf16=S["ty16"][lo:hi], stats=S["tst"][lo:hi])
+        L.gemm_bf16_nt(S["ty16"][lo:hi], hd["w"], L.EPI_F32, bias=hd["b"], out_f32=S["logits"][lo:hi])
+
+    # ------------------------------------------------------------------------------------------ trainable LM head
+    @_bound
+    def _refresh_head(self):
+        """The head's kernel operands from its fp32 group (one launch): 16-bit W and W^T of transform.dense, the padded bias."""
+        g, hd = self.lm, self.head
+        L.lm_head_refresh(g.view(g.names[0]), g.view(g.names[4]), hd["t"]["w"], hd["t"]["wT"], hd["b"])
+
+    def _alloc_head_grads(self):
+        """Partial-sum buffers and the reduce table of the head's four vector gradients (a sub-step has R rows, whatever the
+        step form), and the head's p | m | v backup of sub-step A under the dynamic loss scale."""
+        dev, H, Vp, g = self.dev, self.H, self.Vp, self.lm
+        slabs = L.vector_grad_workspace_elems(self.R, H) // H
+        self.hg = dict(bias=torch.empty(slabs * Vp, device=dev), db=torch.empty(slabs * H, device=dev),
+                       gamma=torch.empty(slabs * H, device=dev), beta=torch.empty(slabs * H, device=dev))
+        ob = g.offsets[g.names[4]]
+        assert ob % 4 == 0 and g.g.numel() >= ob + Vp
+        self.hg_table = L.make_vgrad_jobs([(self.hg["bias"], slabs, g.g[ob:ob + Vp]), (self.hg["db"], slabs, g.view(g.names[1], g.g)),
+                                           (self.hg["gamma"], slabs, g.view(g.names[2], g.g)),
+                                           (self.hg["beta"], slabs, g.view(g.names[3], g.g))], dev)
+        self.head_bak = torch.empty(3 * g.p.numel(), device=dev) if self.dynamic_scale else None
+        # diagnostics: a tensor of the gradient buffer's size set here receives the head's gradient of sub-step A (L_1), which
+        # sub-step B's otherwise overwrites within the step
+        self.grad_a_probe: Optional[torch.Tensor] = None
+
+    def _head_step_a(self):
+        """Sub-step A's optimizer step on the head (tick 2b).  Dynamic scale: skipped on flag A as far as it is known here (the
+        loss, the head's own gradients); the old p | m | v are kept for _dat_tail's restore, should adapter_1's backward raise
+        the flag later.  The counters are ticked once, at the end of the step."""
+        if self.grad_a_probe is not None:
+            self.grad_a_probe.copy_(self.lm.g)
+        if self._dyn():
+            self._adamw_many([self._adamw_group(self.lm, skip_if=(self.ovf_flags[1:2],), bak=self.head_bak, bak_mode=1)])
+        else:
+            self._adamw_many([self._adamw_group(self.lm)])
+        self._refresh_head()
 
     # ------------------------------------------------------------------------------------------ backward
     def _bert_bwd(self, T, S, m0: int, mode: str, M, nb, Sq, self_mask, causal, enc16, enc_rows, Skv, enc_mask, d_out,
@@ -763,7 +863,7 @@ class AlbefDatEngine(LocalUpdateEngine):
     def _backward_text(self, mode: str, teacher_logits, pass_id=None):
         """Loss, LM head, decoder and text encoder backward of the pass `mode`; leaves d(image_embeds) in its scratch set.
         mode "both": the two passes stacked, each half's MKD teacher the OTHER half's logits (teacher_logits unused)."""
-        S, g, hd, H = self.acts[mode], self.gs[mode], self.head, self.H
+        S, g = self.acts[mode], self.gs[mode]
         t = self.tx["both" if mode == "both" else "single"]
         R, R1 = t["R"], self.R
         if mode == "both":       # L_0 = (loss_0 + KL(logits_0 || logits_1)) / 2 on rows [0, R), L_1 likewise on rows [R, 2R)
@@ -775,12 +875,59 @@ class AlbefDatEngine(LocalUpdateEngine):
         else:
             L.lm_loss_fwd_bwd(S["logits"], teacher_logits, self.labels, self.row_w, self.V, 3.0, 9.0 / self.N, g["dlogits"],
                               S["loss"], row_kl=self.row_kl, **self._scale_in(mode))
-        # LM head backward (frozen): logits = LN(gelu(dense(h))) W_emb^T
-        L.gemm_bf16_nt(g["dlogits"], hd["wT"], L.EPI_BF16, out_bf16=g["b1"][:R])
-        L.layernorm_bwd_dx(S["tg"], S["tst"], hd["lng"], R, H, dy_bf16=g["b1"][:R], out_f32=g["d1"][:R])
-        L.gelu_bwd(S["tu"], g["d1"][:R], g["d2"][:R])
-        L.cvt_f32_bf16(g["d2"][:R], g["b1"][:R])
-        L.gemm_bf16_nt(g["b1"][:R], hd["t"]["wT"], L.EPI_F32, out_f32=g["d1"][:R])
+        self._lm_head_bwd(S, g, 0, R)
+        self._towers_bwd(mode, pass_id)
+
+    def _lm_head_bwd(self, S, g, lo: int, hi: int, grads: bool = False, flag=None):
+        """LM head backward of rows [lo, hi): logits = LN(gelu(dense(h))) W_emb^T; dlogits -> d(selected decoder rows) in
+        g["d1"][lo:hi].  grads (a sub-step of a step that trains the head; flag: that sub-step's overflow flag under the dynamic
+        scale): the gradients of the head's five tensors go into the head group's gradient buffer, unscaled --
+          d bias        column sums of the 16-bit dlogits [rows, Vp]                      feddat_colsum_partial
+          d gamma, beta sum_r dy xhat, sum_r dy of the transform LayerNorm (dy fp32)      feddat_ln_param_grad_partial
+          d dense.bias  column sums of d2 = d(dense output), fp32                         feddat_colsum_partial
+            (the four folded, unscaled and inf-checked in ONE feddat_vector_grad_reduce)
+          d dense.W     d2^T x over the rows, x = the fp32 selected decoder rows          feddat_head_gemm (fp32 MFMA, unscaled by alpha)
+        all fixed-order sums.  d dense.W has no inf check of its own: it is non-finite only where d2 is (x is a LayerNorm
+        output), and then so are d2's column sums, which are checked."""
+        hd, H, n = self.head, self.H, hi - lo
+        train = bool(grads)
+        dl, b1, d1, d2 = g["dlogits"][lo:hi], g["b1"][lo:hi], g["d1"][lo:hi], g["d2"][lo:hi]
+        if train:
+            # dy = d(LayerNorm output) stays fp32 here (the frozen-head path rounds it to the operand format) and is formed with
+            # the decoder weight to about twice the operand's mantissa (two products): it feeds the sums for gamma / beta and,
+            # through d2, those for transform.dense
+            dy = g["d3"][lo:hi]
+            L.gemm_bf16_nt(dl, hd["wT"], L.EPI_F32, out_f32=g["d4"][lo:hi])
+            L.gemm_bf16_nt(dl, hd["wT_lo"], L.EPI_RESID_F32, resid=g["d4"][lo:hi], out_f32=dy)       # + dlogits (W_emb - W_emb16)
+            L.colsum_partial(dl, self.hg["bias"])
+            L.ln_param_grad_partial(dy, S["tg"][lo:hi], S["tst"][lo:hi], self.hg["beta"], self.hg["gamma"])
+            L.layernorm_bwd_dx(S["tg"][lo:hi], S["tst"][lo:hi], hd["lng"], n, H, dy_f32=dy, out_f32=d1)
+        else:
+            L.gemm_bf16_nt(dl, hd["wT"], L.EPI_BF16, out_bf16=b1)
+            L.layernorm_bwd_dx(S["tg"][lo:hi], S["tst"][lo:hi], hd["lng"], n, H, dy_bf16=b1, out_f32=d1)
+        L.gelu_bwd(S["tu"][lo:hi], d1, d2)
+        if train:
+            L.colsum_partial(d2, self.hg["db"])
+            key = ("head-wgrad", d2.data_ptr(), S["hsel"].data_ptr(), lo, self._dyn())
+            if key not in self._segs_cache:
+                gw = self.lm.view(self.lm.names[0], self.lm.g)
+                us = dict(alpha=1.0, alpha_dev=self.scaler_f[1:2]) if self._dyn() else dict(alpha=1.0 / self.loss_scale)
+                # out[i, j] = sum_r d2[r, i] x[r, j]: A[i, k] = d2[k, i], B[k, j] = x[k, j]
+                self._segs_cache[key] = L.ht_job(d2, 1, H, S["hsel"][lo:hi], H, 1, H, H, n, gw, **us)
+            L.head_gemm(self._segs_cache[key])
+        L.cvt_f32_bf16(d2, b1)
+        L.gemm_bf16_nt(b1, hd["t"]["wT"], L.EPI_F32, out_f32=d1)
+        if train:
+            table, njobs, max_n = self.hg_table
+            us = dict(unscale=1.0, unscale_dev=self.scaler_f[1:2]) if self._dyn() else dict(unscale=1.0 / self.loss_scale)
+            L.vector_grad_reduce(table, njobs, max_n, nonfinite=flag, **us)
+
+    def _towers_bwd(self, mode: str, pass_id=None):
+        """From the gradient of the selected decoder rows (g["d1"], left by _lm_head_bwd) down: decoder and text encoder
+        backward of the pass `mode`; leaves d(image_embeds) in its scratch set."""
+        S, g, H = self.acts[mode], self.gs[mode], self.H
+        t = self.tx["both" if mode == "both" else "single"]
+        R = t["R"]
         L.gather_rows(g["d1"][:R], t["unsel_idx"], dst_f32=g["d_dec"])          # zero rows at the last position of each answer
         emb16 = self.emb16_both if mode == "both" else S["vit"]["emb16"]
         self._bert_bwd(self.dec, S["dec"], self.vd + self.el, mode, t["Ma"], t["na"], self.La, t["amask8"], True,
@@ -806,16 +953,127 @@ class AlbefDatEngine(LocalUpdateEngine):
         self._start_local_update(steps_per_epoch, num_epochs, warmup_ratio, {"adapter_0": (1, 0)})
 
     def _graph_switches(self):
-        return (self.dropout, self.batch_text)
+        return (self.dropout, self.batch_text, self.train_lm_head)
 
     def _named_groups(self):
-        return [("adapter_0", self.ad[0]), ("adapter_1", self.ad[1])]
+        groups = [("adapter_0", self.ad[0]), ("adapter_1", self.ad[1])]
+        return groups + [("lm_head", self.lm)] if self.train_lm_head else groups
+
+    def _state_groups(self):
+        return list(self.ad) + ([self.lm] if self.train_lm_head else [])
 
     def _extra_step_state(self):
         return [self.drop_ctr]
 
     @_bound
+    def _capture(self):
+        super()._capture()
+        if self.train_lm_head:      # the head's tensors are back at their state before the capture: so are its operand copies
+            self._refresh_head()
+            torch.cuda.synchronize()
+
+    @_bound
+    def load_tensors(self, tensors: Dict[str, torch.Tensor]):
+        super().load_tensors(tensors)
+        if self.train_lm_head and any(n in self.lm.offsets for n in tensors):
+            self._refresh_head()
+
+    def repack(self):
+        super().repack()
+        if self.train_lm_head:
+            self._refresh_head()
+
+    def _step_kernels_head(self):
+        """The step with a trainable LM head (task_trainer.py:280-330; the head is in the optimizer of BOTH sub-steps):
+          1. towers of both passes up to the decoder output, LM head with the OLD head -> logits_all (P0), logits_1 (P1)
+          2. L_1; LM-head backward of the P1 rows through the old head; the head's gradients; AdamW on the head at tick 2b
+          3. the head's operand copies rebuilt (feddat_lm_head_refresh)
+          4. the LM head AGAIN on the gated pass's decoder output -- only the head changed, the towers are not re-run (with
+             dropout P2's text towers are a pass of their own anyway: it simply runs here, after the update) -> logits_0
+          5. L_0 against the PRE-update logits_1; LM-head backward of the gated rows through the UPDATED head; its gradients
+          6. the towers' backward of both passes (adapter_1's starts on the second stream as soon as 2. is done)
+          7. _dat_tail with the head: adapter_1 (2b), head (2b + 1), adapter_0 (2b + 1), GradScaler's predicates; operands again.
+        An adapter_0 that left the optimizer (server flags after an eval) drops its towers' backward only: the reference's
+        optimizer holds the head either way, so 5. still runs."""
+        cur = torch.cuda.current_stream()
+        if self.side is None:
+            self.side = torch.cuda.Stream(device=self.dev)
+        side = self.side
+        drop = self.dropout > 0
+        dyn = self._dyn()
+        fB, fA = (self.ovf_flags[0:1], self.ovf_flags[1:2]) if dyn else (None, None)
+        R = self.R
+        Sg, S1, gg, g1 = self.acts["gating"], self.acts["adapter_1"], self.gs["gating"], self.gs["adapter_1"]
+
+        def loss(logits, teacher, dl, own):
+            L.lm_loss_fwd_bwd(logits, teacher, self.labels, self.row_w, self.V, 3.0, 9.0 / self.N, dl, self.acts[own]["loss"],
+                              row_kl=self.row_kl, **self._scale_in(own))
+        self._vit_fwd(Sg, "gating", "prefix")
+        side.wait_stream(cur)
+        if self.batch_text and self.opt_adapters == (0, 1):
+            # the stacked form: rows [0, R) gated, [R, 2R) adapter_1 of one text-side pass
+            with torch.cuda.stream(side):
+                self._vit_fwd(Sg, "gating", "suffix")
+            self._vit_fwd(S1, "adapter_1", "suffix")
+            cur.wait_stream(side)
+            lg = self._forward_text("both")
+            S, g = self.acts["both"], self.gs["both"]
+            loss(lg[R:], lg[:R], g["dlogits"][R:], "adapter_1")
+            self._lm_head_bwd(S, g, R, 2 * R, True, fA)
+            self._head_step_a()
+            self._lm_head_fwd(S, 0, R)
+            loss(lg[:R], lg[R:], g["dlogits"][:R], "gating")
+            self._lm_head_bwd(S, g, 0, R, True, fB)
+            self._towers_bwd("both")
+            d_img = g["d_img"]
+            side.wait_stream(cur)
+            with torch.cuda.stream(side):
+                self._vit_bwd(Sg, "gating", d_img[:self.Mi])
+                self._wgrad_reduce("gating")
+            self._vit_bwd(S1, "adapter_1", d_img[self.Mi:])
+            self._wgrad_reduce("adapter_1")
+            self._wgrad_reduce("both")
+            cur.wait_stream(side)
+        else:
+            with torch.cuda.stream(side):
+                self._vit_fwd(Sg, "gating", "suffix")
+                if drop:       # P0 under its own masks; the gated text towers run again for P2 below
+                    self.logits_all.copy_(self._forward_text("gating", 0))
+                    teacher = self.logits_all
+                else:
+                    teacher = self._forward_text("gating")
+            self._vit_fwd(S1, "adapter_1", "suffix")
+            logits_1 = self._forward_text("adapter_1", 1 if drop else None)
+            cur.wait_stream(side)
+            loss(logits_1, teacher, g1["dlogits"], "adapter_1")
+            self._lm_head_bwd(S1, g1, 0, R, True, fA)
+            self._head_step_a()
+            side.wait_stream(cur)
+            with torch.cuda.stream(side):
+                self._towers_bwd("adapter_1", 1 if drop else None)
+                self._vit_bwd(S1, "adapter_1", g1["d_img"])
+                self._wgrad_reduce("adapter_1")
+            if drop:
+                logits_0 = self._forward_text("gating", 2)
+            else:
+                self._lm_head_fwd(Sg, 0, R)
+                logits_0 = Sg["logits"]
+            loss(logits_0, logits_1, gg["dlogits"], "gating")
+            self._lm_head_bwd(Sg, gg, 0, R, True, fB)
+            if 0 in self.opt_adapters:
+                self._towers_bwd("gating", 2 if drop else None)
+                self._vit_bwd(Sg, "gating", gg["d_img"])
+                self._wgrad_reduce("gating")
+            cur.wait_stream(side)
+        self._dat_tail(self.lm, self.head_bak)
+        self._refresh_head()
+        if drop:
+            L.step_tick(self.drop_ctr, 1, 0)
+
+    @_bound
     def _step_kernels(self):
+        if self.train_lm_head:
+            return self._step_kernels_head()
         # The two passes are independent up to the loss and from the loss down to their adapters, so they run side by
         # side on two streams (separate activation, scratch and weight-gradient workspaces per pass; inside a captured
         # step the fork / join become graph edges): the text towers' launches are small (25-token questions, 4-token

@@ -27,11 +27,15 @@ class ALBEFContinualLearner:
     BERT_LOCAL_PATH = "./models/bert-base-uncased"       # albef.py:38
 
     def __init__(self, params: Dict[str, torch.Tensor], device, batch_size: int, n_answers: int, q_len: int = 25,
-                 a_len: int = 4, lr: float = 1e-4, tokenizer_vocab=None, **dims):
+                 a_len: int = 4, lr: float = 1e-4, tokenizer_vocab=None, train_lm_head: bool = False, **dims):
+        """train_lm_head: the LM head text_decoder.cls.predictions.* trains and is personal, as in the reference (main.py:127-128,
+        247-250; AlbefDatEngine); state_dict() then carries its five tensors (not the tied aliases decoder.weight / decoder.bias).
+        Off by default: the head stays frozen and state_dict() holds the adapters alone."""
         self.device = torch.device(device)
+        self.train_lm_head = bool(train_lm_head)
         self._vocab, self._tokenizer = tokenizer_vocab, None
         self.engine = AlbefDatEngine(params, self.device, batch=batch_size, n_answers=n_answers, q_len=q_len, a_len=a_len,
-                                     lr=lr, **dims)
+                                     lr=lr, train_lm_head=self.train_lm_head, **dims)
         self.gating, self.active = False, "adapter_1"
         # prepare_model's initial state (main.py:157-159 + adapter.py:55-58): adapter_0/1 trainable, adapter_2 frozen
         self.adapter_requires_grad = {0: True, 1: True, 2: False}
@@ -64,8 +68,7 @@ class ALBEFContinualLearner:
         self.engine.load_tensors({k: v for k, v in sd.items() if k in own})
 
     def after_load(self):
-        for a in range(3):
-            self.engine.repack_adapter(a)
+        self.engine.repack()
 
     # ---- the reference's batch schema: questions / answers as strings (albef.py:52-73) ----
     @property
@@ -142,10 +145,11 @@ class ALBEFContinualLearner:
 
 def create_albef_continual_learner_model(params: Dict[str, torch.Tensor], device, batch_size: int, n_answers: int,
                                          q_len: int = 25, a_len: int = 4, lr: float = 1e-4, tokenizer_vocab=None,
-                                         **dims) -> ALBEFContinualLearner:
+                                         train_lm_head: bool = False, **dims) -> ALBEFContinualLearner:
     """albef.py:255-273 (the ALBEF.pth checkpoint is passed in as a tensor dict: feddat_amd.weights.load_albef_pretrained
     reads it from a local file; there is no hub access here)."""
-    return ALBEFContinualLearner(params, device, batch_size, n_answers, q_len, a_len, lr, tokenizer_vocab=tokenizer_vocab, **dims)
+    return ALBEFContinualLearner(params, device, batch_size, n_answers, q_len, a_len, lr, tokenizer_vocab=tokenizer_vocab,
+                                 train_lm_head=train_lm_head, **dims)
 
 
 def convert_batch_to_albef_input_dict(batch):

@@ -391,7 +391,52 @@ __global__ __launch_bounds__(64) void rank_slab_loss_kernel(const float* __restr
     answer_loss[first + i] = acc;
 }
 
+// The trainable LM head's kernel operands from its fp32 master tensors, one launch (feddat_lm_head_refresh): blocks
+// [0, (H / 32)^2) each take one 32 x 32 tile of transform.dense.weight [H, H] -- 16-byte loads, the tile stored as it is (W, the
+// forward operand) and transposed through LDS (W^T, the operand of dX), both as 8-byte stores of four operand-format values, the
+// conversions those of cvt_kernel / transpose_cvt_kernel (embed_misc.hip): equal bits; the blocks behind them write the
+// vocabulary bias padded with zeros to Vp, four floats per thread.
+constexpr int LHR_T = 32;
+__global__ __launch_bounds__(256) void lm_head_refresh_kernel(const float* __restrict__ w, const float* __restrict__ bias, int H,
+                                                              int V, int Vp, bf16* __restrict__ w16, bf16* __restrict__ wT16,
+                                                              float* __restrict__ bias_pad) {
+    __shared__ float tile[LHR_T][LHR_T + 1];
+    const int tpr = H / LHR_T, ntiles = tpr * tpr;
+    const int blk = blockIdx.x, tid = threadIdx.x;
+    if (blk >= ntiles) {
+        const int i = ((blk - ntiles) * 256 + tid) * 4;
+        if (i >= Vp) return;                      // (Vp % 4 == 0: a quad is whole or absent)
+        f32x4 v;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = i + e < V ? bias[i + e] : 0.f;
+        *reinterpret_cast<f32x4*>(bias_pad + i) = v;
+        return;
+    }
+    const int r0 = (blk / tpr) * LHR_T, c0 = (blk % tpr) * LHR_T;
+    const int a = tid >> 3, q = (tid & 7) * 4;      // 32 rows x 8 quads
+    const f32x4 v = *reinterpret_cast<const f32x4*>(w + (size_t)(r0 + a) * H + c0 + q);
+    *reinterpret_cast<bf16x4*>(w16 + (size_t)(r0 + a) * H + c0 + q) = cvt4(v);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) tile[a][q + e] = v[e];
+    __syncthreads();
+    // row c0 + a of W^T = column c0 + a of W, its elements r0 + q .. r0 + q + 3
+    const f32x4 t = {tile[q][a], tile[q + 1][a], tile[q + 2][a], tile[q + 3][a]};
+    *reinterpret_cast<bf16x4*>(wT16 + (size_t)(c0 + a) * H + r0 + q) = cvt4(t);
+}
+
 }  // namespace
+
+extern "C" int feddat_lm_head_refresh(const float* w, const float* bias, int H, int V, int Vp, void* w_bf16, void* wT_bf16,
+                                      float* bias_pad, hipStream_t stream) {
+    FD_CHECK_ARG(w && bias && w_bf16 && wT_bf16 && bias_pad);
+    FD_CHECK_ARG(H > 0 && H % LHR_T == 0 && H <= 8192 && V > 0 && Vp >= V && Vp % 4 == 0 && Vp < (1 << 30));
+    FD_CHECK_ARG((((uintptr_t)w | (uintptr_t)bias_pad) & 15) == 0 && ((uintptr_t)bias & 3) == 0);
+    FD_CHECK_ARG((((uintptr_t)w_bf16 | (uintptr_t)wT_bf16) & 7) == 0);
+    const int tiles = (H / LHR_T) * (H / LHR_T), bias_blocks = (Vp / 4 + 255) / 256;
+    hipLaunchKernelGGL(lm_head_refresh_kernel, dim3(tiles + bias_blocks), dim3(256), 0, stream, w, bias, H, V, Vp, (bf16*)w_bf16,
+                       (bf16*)wT_bf16, bias_pad);
+    FD_LAUNCH_RET();
+}
 
 extern "C" int feddat_albef_pad_questions(float* image, long* question_ids, long* question_mask, int nq, int B, long image_elems,
                                           int Lq, hipStream_t stream) {

@@ -188,6 +188,7 @@ _SIGS = {
     "feddat_albef_pad_questions": [vp, vp, vp, i32, i32, i64, i32, vp],
     "feddat_rank_slab_gather": [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i64, vp],
     "feddat_rank_slab_loss": [vp, vp, i32, i32, i32, i32, i32, i32, vp],
+    "feddat_lm_head_refresh": [vp, vp, i32, i32, i32, vp, vp, vp, vp],
     "feddat_gather_rows": [vp, vp, vp, vp, i32, i32, vp],
     "feddat_segment_sum_rows": [vp, vp, vp, i32, i32, i32, vp],
     "feddat_adamw_flat": [vp, vp, vp, vp, i64, vp, vp, i32, vp, f32, i32, i32, f32, f32, f32, vp],
@@ -1073,6 +1074,24 @@ def rank_slab_loss(scalars, answer_loss, nq: int, k: int, B: int, N: int, La: in
     assert answer_loss.dtype == torch.float32 and answer_loss.is_contiguous() and answer_loss.numel() == nq * k
     _chk(load().feddat_rank_slab_loss(_p(scalars), _p(answer_loss), int(nq), int(k), int(B), int(N), int(La), int(slab), _stream()),
          "feddat_rank_slab_loss")
+
+
+def lm_head_refresh(w, bias, w16, wT16, bias_pad):
+    """feddat_lm_head_refresh: the trainable LM head's fp32 master tensors (w = transform.dense.weight [H, H], bias =
+    predictions.bias [V], views of a flat group) -> the step's operands in one launch: w16 / wT16 [H, H] in the bound library's
+    operand format (the bits of cvt_f32_bf16 / transpose_f32_bf16) and bias_pad [Vp] = bias followed by zeros."""
+    _dev(w, bias, w16, wT16, bias_pad)
+    H = w.shape[0]
+    fmt = OPERAND_DTYPE[current_operands()]
+    if not (w.dim() == 2 and w.shape[1] == H and w.dtype == torch.float32 and w.is_contiguous() and bias.dim() == 1
+            and bias.dtype == torch.float32 and bias.is_contiguous() and bias_pad.dtype == torch.float32
+            and bias_pad.is_contiguous() and bias_pad.dim() == 1 and bias_pad.numel() >= bias.numel()):
+        raise FeddatHipError("lm_head_refresh: w fp32 [H, H], bias fp32 [V], bias_pad fp32 [Vp >= V], all contiguous")
+    for t in (w16, wT16):
+        if not (t.dtype == fmt and tuple(t.shape) == (H, H) and t.is_contiguous()):
+            raise FeddatHipError(f"lm_head_refresh: w16 / wT16 must be contiguous [{H}, {H}] tensors of {fmt}")
+    _chk(load().feddat_lm_head_refresh(_p(w), _p(bias), H, bias.numel(), bias_pad.numel(), _p(w16), _p(wT16), _p(bias_pad),
+                                       _stream()), "feddat_lm_head_refresh")
 
 
 def dropout(x, drop, *, resid=None, out_f32=None, out_bf16=None):

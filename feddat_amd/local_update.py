@@ -34,7 +34,10 @@ def _bound(fn):
 class FlatGroup:
     """A set of named fp32 tensors living back-to-back in one flat device buffer (+ grad, Adam m/v, segment table)."""
 
-    def __init__(self, names_shapes: Sequence, device, with_opt: bool):
+    def __init__(self, names_shapes: Sequence, device, with_opt: bool, pad: int = 0):
+        """pad: floats kept behind the last tensor besides the quad padding (they belong to no name and stay 0.0f like it): the
+        ALBEF LM head's vocabulary bias, last in its group, is followed by the padding of the vocabulary axis, so that its
+        gradient can be reduced at the padded width."""
         self.names = [n for n, _ in names_shapes]
         self.shapes = {n: tuple(s) for n, s in names_shapes}
         self.offsets = {}
@@ -46,7 +49,7 @@ class FlatGroup:
         # the buffers hold a whole number of quads (the multi-group AdamW moves 16 bytes per lane: feddat_adamw_multi wants
         # n % 4 == 0); up to 3 floats behind the last tensor (a head of 3129 labels: 5 993 529 floats) stay 0.0f for good --
         # zero gradient, zero moments, and they belong to no name
-        alloc = (off + 3) // 4 * 4
+        alloc = (off + int(pad) + 3) // 4 * 4
         self.p = torch.zeros(alloc, device=device)
         if with_opt:
             self.g = torch.zeros(alloc, device=device)

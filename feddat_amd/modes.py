@@ -5,6 +5,8 @@ module does the same on the keys it is given.
 
   mode       trainable                      communicated (FedAvg)     personal (kept per client)
   dat        adapter_0, adapter_1, heads    adapter_1                 heads, adapter_0, adapter_2
+             (heads: ViLT's task_layer.* ('task'); ALBEF's text_decoder.cls.predictions.* ('.cls.'), present in an ALBEF state dict
+             only when the model was built with train_lm_head=True)
   adapter    adapter, heads                 every 'adapter' key       heads ('task')
   bias       every 'bias' key, heads        every 'bias' key          heads ('task')
   norm       every 'norm' key, heads        every 'norm' key          heads ('task')
@@ -43,9 +45,10 @@ def mode_names(keys: Sequence[str], mode: str) -> Dict[str, List[str]]:
         raise L.FeddatHipError(f"optimizer_mode must be one of {MODES}, got {mode!r}")
     keys = list(keys)
     if mode == "dat":
-        return dict(trainable=[k for k in keys if "task" in k or "adapter_0" in k or "adapter_1" in k],
+        # '.cls.': the ALBEF decoder's LM head (main.py:127-128,247-250); no ViLT key contains it
+        return dict(trainable=[k for k in keys if "task" in k or ".cls." in k or "adapter_0" in k or "adapter_1" in k],
                     communicated=[k for k in keys if "adapter_1" in k],
-                    personal=[k for k in keys if "task" in k or "adapter_0" in k or "adapter_2" in k])
+                    personal=[k for k in keys if "task" in k or ".cls." in k or "adapter_0" in k or "adapter_2" in k])
     sub = mode          # "adapter" | "bias" | "norm": the substring main.py matches is the mode's own name
     return dict(trainable=[k for k in keys if sub in k or "task" in k],
                 communicated=[k for k in keys if sub in k],

@@ -353,6 +353,11 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--albef_dropout", type=float, default=0.1,
                    help="hidden / attention-probability dropout of the ALBEF BERT towers under train_step (the reference's "
                         "model.train() with src/configs/model_configs.py:44-46); 0 = the deterministic parity configuration")
+    p.add_argument("--albef_train_lm_head", action="store_true",
+                   help="ALBEF only: train each client's LM head text_decoder.cls.predictions.* (bias, transform.dense, "
+                        "transform.LayerNorm) as the reference's prepare_model does (main.py:247-250); the head is personal "
+                        "(main.py:127-128): it rides with adapter_0 / adapter_2 in the client's personal parameters and is never "
+                        "averaged.  Off by default: the head stays frozen")
     p.add_argument("--albef_dims", type=str, default="",
                    help="ALBEF only: override depths for quick runs, e.g. vit_depth=2,enc_layers=3,fusion_layer=1,dec_layers=2")
     p.add_argument("--no_hip_graph", dest="hip_graph", action="store_false")
@@ -396,6 +401,9 @@ def main(argv=None):
                                "row 13)")
     if mode != "dat" and "albef" in args.encoder_name:
         raise L.FeddatHipError("ALBEF supports only --optimizer_mode dat (adapter, bias and norm are ViLT modes here)")
+    if args.albef_train_lm_head and "albef" not in args.encoder_name:
+        raise L.FeddatHipError("--albef_train_lm_head is an ALBEF option (--encoder_name albef_no_distill): ViLT has no LM head, "
+                               "its task heads always train")
     if args.synthetic_last_batch:
         if "albef" in args.encoder_name:
             raise L.FeddatHipError("--synthetic_last_batch is a ViLT option: the ALBEF engine runs full batches only (the "
@@ -483,7 +491,7 @@ def main(argv=None):
             params = albef_spec.random_init(seed=args.seed, image=args.image_size, **dims)
         model = create_albef_continual_learner_model(params, dev, args.batch_size, args.batch_size, lr=args.lr,
                                                      image=args.image_size, dropout=args.albef_dropout,
-                                                     seed=args.seed + 7919 * rank,
+                                                     seed=args.seed + 7919 * rank, train_lm_head=args.albef_train_lm_head,
                                                      operands={"fp16": "f16", "bf16": "bf16"}[args.mixed_precision], **dims)
         Trainer = AlbefTaskTrainer
     else:

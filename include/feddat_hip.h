@@ -675,6 +675,16 @@ int feddat_rank_slab_gather(const long* topk_ids, const long* list_ids, const lo
                             int B, int N, int La, int slab, long pad_id, hipStream_t stream);
 int feddat_rank_slab_loss(const float* scalars, float* answer_loss, int nq, int k, int B, int N, int La, int slab,
                           hipStream_t stream);
+/* The trainable ALBEF LM head (AlbefDatEngine(train_lm_head=True): text_decoder.cls.predictions.*, main.py:247-250) -- addition
+ * within ABI 8 (csrc/albef_misc.hip).  feddat_lm_head_refresh: ONE launch turns the head's fp32 master tensors into the operands
+ * the step's kernels read: w_bf16 [H, H] = transform.dense.weight w [H, H] in the build's 16-bit operand format (what
+ * feddat_cvt_f32_bf16 gives, bit for bit), wT_bf16 [H, H] = its transpose (feddat_transpose_f32_bf16's bits), bias_pad [Vp] =
+ * predictions.bias [V] followed by Vp - V zeros (the vocabulary axis padded to the GEMM's tile).  Called after each of the two
+ * head updates of a train_step; plain loads and vector stores, no atomics, graph-capturable.  FEDDAT_EINVAL (nothing launched)
+ * on a NULL pointer, H <= 0, H % 32 != 0, H > 8192, V <= 0, Vp < V, Vp % 4 != 0, Vp >= 2^30, w or bias_pad not 16-byte aligned,
+ * bias not 4-byte aligned (it may start anywhere in a flat fp32 buffer), w_bf16 or wT_bf16 not 8-byte aligned. */
+int feddat_lm_head_refresh(const float* w, const float* bias, int H, int V, int Vp, void* w_bf16, void* wT_bf16,
+                           float* bias_pad, hipStream_t stream);
 
 
 /* ---------------------------------------------------------------------------------------------
