@@ -511,7 +511,8 @@ class AlbefDatEngine(LocalUpdateEngine):
         img = batch["image"]
         if tuple(img.shape) != tuple(self.inp["image"].shape):
             raise L.FeddatHipError(f"engine built for image {tuple(self.inp['image'].shape)}, got {tuple(img.shape)}")
-        self.inp["image"].copy_(img, non_blocking=True)
+        if img.data_ptr() != self.inp["image"].data_ptr():      # (the image transform writes into this very buffer)
+            self.inp["image"].copy_(img, non_blocking=True)
         qi, qm, ai, am, wt = (batch[k] for k in ("question_ids", "question_mask", "answer_ids", "answer_mask", "weights"))
         lq, n, la = qi.shape[1], ai.shape[0], ai.shape[1]
         if qi.shape[0] != B or tuple(qm.shape) != tuple(qi.shape) or tuple(am.shape) != tuple(ai.shape) or wt.shape[0] != n:
@@ -1226,7 +1227,8 @@ class AlbefDatEngine(LocalUpdateEngine):
         answer_ids = answer_ids.to(dev, torch.int64).contiguous()
         answer_mask = answer_mask.to(dev, torch.int64).contiguous()
         inp = self.inp
-        inp["image"][:nq].copy_(img, non_blocking=True)
+        if img.data_ptr() != inp["image"].data_ptr():
+            inp["image"][:nq].copy_(img, non_blocking=True)
         if lq < Lq:
             inp["question_ids"].fill_(self.pad_id)
             inp["question_mask"].zero_()

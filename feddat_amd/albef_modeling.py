@@ -12,7 +12,10 @@ Batches are the reference's (convert_batch_to_albef_input_dict, albef.py:275-286
 [str], "answers": [str], "weights": [n], "n": answers per question, "alpha", "train"} -- tokenised ONCE per batch by the device
 WordPiece tokenizer (the reference's BertTokenizer runs inside every forward pass: albef.py:56-57,62-64) and embedded in the
 engine's static frame -- or already-tokenised dicts (question_ids / question_mask, answer_ids / answer_mask, weights, k), of
-any length up to the frame (AlbefDatEngine.set_batch)."""
+any length up to the frame (AlbefDatEngine.set_batch).  "images" (or "image") may also be a LIST of decoded RGB images -- uint8
+[H, W, 3] arrays / tensors or PIL images, as the image datasets hand them out: the reference's whole image transform (the
+datasets' bilinear Resize(384, max_size=640), then bicubic Resize((R, R)), ToTensor, Normalize) then runs on the device,
+straight into the engine's image buffer (image_processing.AlbefImageTransform)."""
 from __future__ import annotations
 
 from typing import Dict, List, Sequence
@@ -27,13 +30,17 @@ class ALBEFContinualLearner:
     BERT_LOCAL_PATH = "./models/bert-base-uncased"       # albef.py:38
 
     def __init__(self, params: Dict[str, torch.Tensor], device, batch_size: int, n_answers: int, q_len: int = 25,
-                 a_len: int = 4, lr: float = 1e-4, tokenizer_vocab=None, train_lm_head: bool = False, **dims):
-        """train_lm_head: the LM head text_decoder.cls.predictions.* trains and is personal, as in the reference (main.py:127-128,
+                 a_len: int = 4, lr: float = 1e-4, tokenizer_vocab=None, train_lm_head: bool = False,
+                 dataset_resize: bool = True, **dims):
+        """dataset_resize: image LISTS pass the image datasets' Resize(384, max_size=640) first (cocoimages_dataset_crossvqas.py:83,
+        108-109: every ALBEF image does); False for images that already went through it.
+        train_lm_head: the LM head text_decoder.cls.predictions.* trains and is personal, as in the reference (main.py:127-128,
         247-250; AlbefDatEngine); state_dict() then carries its five tensors (not the tied aliases decoder.weight / decoder.bias).
         Off by default: the head stays frozen and state_dict() holds the adapters alone."""
         self.device = torch.device(device)
         self.train_lm_head = bool(train_lm_head)
         self._vocab, self._tokenizer = tokenizer_vocab, None
+        self.dataset_resize, self._image_transform = bool(dataset_resize), None
         self.engine = AlbefDatEngine(params, self.device, batch=batch_size, n_answers=n_answers, q_len=q_len, a_len=a_len,
                                      lr=lr, train_lm_head=self.train_lm_head, **dims)
         self.gating, self.active = False, "adapter_1"
@@ -95,6 +102,32 @@ class ALBEFContinualLearner:
             raise L.FeddatHipError(f"{what} longer than the engine's frame ({limit} tokens)")
         return enc["input_ids"][:, :longest].contiguous(), enc["attention_mask"][:, :longest].contiguous(), enc["lengths"]
 
+    @property
+    def image_transform(self):
+        if self._image_transform is None:
+            from .image_processing import AlbefImageTransform
+            self._image_transform = AlbefImageTransform(self.device, image=self.engine.img)
+        return self._image_transform
+
+    @staticmethod
+    def image_list(batch: Dict):
+        """The batch's image list, or None when it brings the float tensor."""
+        img = batch["images"] if "images" in batch else batch.get("image")
+        return img if isinstance(img, (list, tuple)) else None
+
+    def _image(self, batch: Dict) -> torch.Tensor:
+        """[n, 3, R, R] float32 on the device.  A list of decoded images is transformed INTO the engine's static image buffer
+        (its first n samples), which set_batch / rank_answer then take without a copy: the tensor is that buffer, good until the
+        next list is processed.  Training batches fill the frame; evaluation batches may be short (rank_answer)."""
+        img = batch["images"] if "images" in batch else batch["image"]
+        if not isinstance(img, (list, tuple)):
+            return img.to(self.device, torch.float32, non_blocking=True)
+        B, train = self.engine.B, batch.get("train", True)
+        if (train and len(img) != B) or not 1 <= len(img) <= B:
+            raise L.FeddatHipError(f"{len(img)} images for an engine of batch size {B}: training batches bring exactly {B}, "
+                                   f"evaluation batches 1 .. {B}")
+        return self.image_transform(img, out=self.engine.inp["image"][:len(img)], dataset_resize=self.dataset_resize)
+
     def process_inputs(self, batch: Dict) -> Dict:
         """ALBEFWrapper.forward's tokenisation (albef.py:52-73) once per batch on the device: TRAIN questions padded to the
         longest and truncated at 25 tokens (albef.py:56), answers padded to the longest; EVAL questions are tokenised WITHOUT
@@ -102,7 +135,11 @@ class ALBEFContinualLearner:
         would change rank_answer's result; the eval path appends [SEP] to every entry of the answer list (albef.py:63) and
         tokenises it the same way."""
         eng = self.engine
-        out = {"image": batch["images"].to(self.device, torch.float32, non_blocking=True), "train": batch.get("train", True)}
+        if "questions" not in batch:         # already tokenised: only the image list is left to do
+            out = {k: v for k, v in batch.items() if k != "images"}
+            out["image"] = self._image(batch)
+            return out
+        out = {"image": self._image(batch), "train": batch.get("train", True)}
         if out["train"]:
             qi, qm, _ = self._tok(list(batch["questions"]), min(25, eng.Lq), True, "question")
         else:
@@ -130,7 +167,7 @@ class ALBEFContinualLearner:
 
     def forward(self, task_key: str, batch: Dict):
         mode = "gating" if self.gating else self.active
-        if "questions" in batch:
+        if "questions" in batch or self.image_list(batch) is not None:
             batch = self.process_inputs(batch)
         if batch.get("train", True):
             loss, logits = self.engine.forward_train_logits(batch, mode)
@@ -145,11 +182,12 @@ class ALBEFContinualLearner:
 
 def create_albef_continual_learner_model(params: Dict[str, torch.Tensor], device, batch_size: int, n_answers: int,
                                          q_len: int = 25, a_len: int = 4, lr: float = 1e-4, tokenizer_vocab=None,
-                                         train_lm_head: bool = False, **dims) -> ALBEFContinualLearner:
+                                         train_lm_head: bool = False, dataset_resize: bool = True,
+                                         **dims) -> ALBEFContinualLearner:
     """albef.py:255-273 (the ALBEF.pth checkpoint is passed in as a tensor dict: feddat_amd.weights.load_albef_pretrained
     reads it from a local file; there is no hub access here)."""
     return ALBEFContinualLearner(params, device, batch_size, n_answers, q_len, a_len, lr, tokenizer_vocab=tokenizer_vocab,
-                                 train_lm_head=train_lm_head, **dims)
+                                 train_lm_head=train_lm_head, dataset_resize=dataset_resize, **dims)
 
 
 def convert_batch_to_albef_input_dict(batch):

@@ -106,6 +106,20 @@ def synthetic_batch(B: int, seed: int, image: int = 384, q_len: int = 25, a_len:
     return out
 
 
+def synthetic_raw_images(n: int, seed: int, image: int = 384):
+    """n decoded RGB images as the image datasets hand them out, before any transform: uint8 [H, W, 3] numpy arrays of mixed
+    sizes and orientations, scaled with the engine's image size (at 384: 480 x 640 and 427 x 640 landscape, 640 x 427 portrait, a
+    384 x 384 square and a 240 x 320 thumbnail that is up-scaled).  Deterministic in (n, seed, image)."""
+    g = torch.Generator().manual_seed(seed)
+    shapes = [(480, 640), (640, 427), (384, 384), (427, 640), (240, 320)]
+    out = []
+    for i in range(n):
+        h, w = shapes[int(torch.randint(0, len(shapes), (1,), generator=g))]
+        h, w = max(1, h * image // 384), max(1, w * image // 384)
+        out.append(torch.randint(0, 256, (h, w, 3), dtype=torch.uint8, generator=g).numpy())
+    return out
+
+
 def synthetic_answer_list(M: int, a_len: int = 4, vocab: int = 30522, seed: int = 0):
     """A stand-in for the task's tokenised answer list (albef.py:62-64): -> (ids [M, a_len], mask [M, a_len]) int64.  Entry i is
     [CLS] t ... [SEP]; the first tokens t are distinct (rank_answer shortlists by the first token's probability, so two entries with

@@ -26,6 +26,7 @@ F8_ACT_SCALE, F8_GRAD_HEADROOM = 0.125, 4.0      # FEDDAT_F8_ACT_SCALE / FEDDAT_
 G8_LO, G8_STEP = -0.135, 0.005        # FEDDAT_G8_LO / FEDDAT_G8_STEP: gelu' ~ G8_LO + G8_STEP * code
 GEMM_OP16, GEMM_FP8, GEMM_FP8MX = range(3)                               # feddat_gemm_route: operand kind
 GEMM_V1, GEMM_MID, GEMM_V2, GEMM_V3, GEMM_DUAL = range(5)                # ... and kernel family (FEDDAT_GEMM_*)
+FILTER_BILINEAR, FILTER_BICUBIC = 2, 3      # FEDDAT_FILTER_*: Pillow's Image.BILINEAR / Image.BICUBIC
 
 ABI_VERSION = 8
 vp, i32, i64, f32, u32 = C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_uint
@@ -203,6 +204,10 @@ _SIGS = {
     "feddat_vilt_key_mask": [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],
     "feddat_vilt_image_workspace_bytes": [vp, vp, vp, vp, i32],
     "feddat_vilt_image_preprocess": [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, i64, vp],
+    "feddat_image_resample_workspace_bytes": [vp, vp, vp, vp, i32, i32],
+    "feddat_image_resample_u8": [vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, i64, vp],
+    "feddat_albef_image_workspace_bytes": [vp, vp, i32, i32],
+    "feddat_albef_image_preprocess": [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, i64, vp],
     "feddat_pos_embed_resize": [vp, vp, i32, i32, i32, i32, vp],
     "feddat_wordpiece_table_entries": [i32],
     "feddat_wordpiece_table_build": [vp, vp, i32, vp, i64],
@@ -1149,6 +1154,85 @@ def text_embed(ids, tts, word, pos, typ, ln_g, ln_b, eps, mod0, h, B, Lt, S, H):
     _dev(ids, h)
     _chk(load().feddat_text_embed(_p(ids), _p(tts), _p(word), _p(pos), _p(typ), _p(ln_g), _p(ln_b), eps, _p(mod0),
                                   _p(h), B, Lt, S, H, _stream()), "feddat_text_embed")
+
+
+def _host_i32(a, n=None):
+    import numpy as np
+    a = np.ascontiguousarray(a, dtype=np.int32)
+    if a.ndim != 1 or (n is not None and a.shape[0] != n):
+        raise FeddatHipError("image sizes are host int arrays of one entry per image")
+    return a
+
+
+def _host_i64(a, n):
+    import numpy as np
+    a = np.ascontiguousarray(a, dtype=np.int64)
+    if a.ndim != 1 or a.shape[0] != n:
+        raise FeddatHipError("image offsets are host int64 arrays of one entry per image")
+    return a
+
+
+def _hp(a):
+    return a.ctypes.data_as(C.c_void_p)
+
+
+def _image_workspace(workspace, need: int, device, what: str):
+    if need < 0:
+        raise FeddatHipError(f"{what} rejected the image sizes")
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=device)
+    _dev(workspace)
+    return workspace
+
+
+def image_resample_u8(images, offsets, heights, widths, out_h, out_w, out, out_offsets, filter=FILTER_BILINEAR, workspace=None):
+    """feddat_image_resample_u8: image i, packed uint8 [h][w][3] at byte offsets[i] of the device buffer `images`, is resampled with
+    Pillow's bilinear / bicubic (FILTER_*) to [out_h][out_w][3] at byte out_offsets[i] of the device buffer `out` (which may be
+    `images` itself where no result overlaps a source).  Sizes and offsets are host arrays.  Every image must lie inside its
+    buffer: checked here, the kernels trust the offsets.  -> the workspace used (hand it back in to reuse it)."""
+    _dev(images, out)
+    if images.dtype != torch.uint8 or out.dtype != torch.uint8 or not images.is_contiguous() or not out.is_contiguous():
+        raise FeddatHipError("image_resample_u8 takes contiguous uint8 device buffers")
+    h = _host_i32(heights)
+    n = h.shape[0]
+    w, oh, ow = _host_i32(widths, n), _host_i32(out_h, n), _host_i32(out_w, n)
+    so, do = _host_i64(offsets, n), _host_i64(out_offsets, n)
+    if n < 1 or min(h.min(), w.min(), oh.min(), ow.min()) < 1 or so.min() < 0 or do.min() < 0:
+        raise FeddatHipError("image_resample_u8: sizes must be >= 1 and offsets >= 0")
+    if int((so + h.astype("int64") * w * 3).max()) > images.numel() or int((do + oh.astype("int64") * ow * 3).max()) > out.numel():
+        raise FeddatHipError("image_resample_u8: an image reaches past the end of its buffer")
+    need = int(load().feddat_image_resample_workspace_bytes(_hp(h), _hp(w), _hp(oh), _hp(ow), n, int(filter)))
+    workspace = _image_workspace(workspace, need, images.device, "feddat_image_resample_workspace_bytes")
+    _chk(load().feddat_image_resample_u8(_p(images), _hp(so), _hp(h), _hp(w), _hp(oh), _hp(ow), _hp(do), n, int(filter), _p(out),
+                                         _p(workspace), workspace.numel(), _stream()), "feddat_image_resample_u8")
+    return workspace
+
+
+def albef_image_preprocess(images, offsets, heights, widths, out, mean, std, workspace=None):
+    """feddat_albef_image_preprocess: n packed uint8 images (as image_resample_u8) -> out fp32 [n, 3, R, R] (contiguous; may be
+    a slice of a larger buffer): bicubic to R x R, x / 255, (x - mean) / std in float32.  -> the workspace used."""
+    import numpy as np
+    _dev(images, out)
+    if images.dtype != torch.uint8 or not images.is_contiguous():
+        raise FeddatHipError("albef_image_preprocess takes a contiguous uint8 device buffer")
+    h = _host_i32(heights)
+    n = h.shape[0]
+    w, so = _host_i32(widths, n), _host_i64(offsets, n)
+    if out.dtype != torch.float32 or not out.is_contiguous() or out.dim() != 4 or out.shape[0] != n or out.shape[1] != 3 \
+            or out.shape[2] != out.shape[3]:
+        raise FeddatHipError(f"albef_image_preprocess writes a contiguous fp32 [n, 3, R, R] tensor of n = {n} images, got "
+                             f"{tuple(out.shape)} {out.dtype}")
+    if n < 1 or min(h.min(), w.min()) < 1 or so.min() < 0 or int((so + h.astype("int64") * w * 3).max()) > images.numel():
+        raise FeddatHipError("albef_image_preprocess: an image is empty or reaches past the end of its buffer")
+    R = int(out.shape[2])
+    m, s = np.ascontiguousarray(mean, dtype=np.float32), np.ascontiguousarray(std, dtype=np.float32)
+    if m.shape != (3,) or s.shape != (3,):
+        raise FeddatHipError("mean and std hold one value per RGB channel")
+    need = int(load().feddat_albef_image_workspace_bytes(_hp(h), _hp(w), n, R))
+    workspace = _image_workspace(workspace, need, images.device, "feddat_albef_image_workspace_bytes")
+    _chk(load().feddat_albef_image_preprocess(_p(images), _hp(so), _hp(h), _hp(w), n, R, _hp(m), _hp(s), _p(out), _p(workspace),
+                                              workspace.numel(), _stream()), "feddat_albef_image_preprocess")
+    return workspace
 
 
 def image_embed_assemble_masked(proj, cls, pos0, pos_grid, patch_mask, attention_mask, mod1, h, key_mask, B, Lt, gh, gw, g, H,

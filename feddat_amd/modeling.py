@@ -197,8 +197,12 @@ class ViltContinualLearner:
 
     def __init__(self, ordered_cl_tasks: List[str], params: Dict[str, torch.Tensor], device, batch_size: int,
                  image_size=384, num_layers: int = 12, lr: float = 1e-4, vocab=None, operands: str = None,
-                 optimizer_mode: str = "dat", num_labels: int = 100, max_patches: Optional[int] = None):
-        """image_size: the engine's static pixel frame, an int (square) or (height, width).
+                 optimizer_mode: str = "dat", num_labels: int = 100, max_patches: Optional[int] = None,
+                 dataset_resize: bool = False):
+        """dataset_resize: images whose shorter side exceeds 384 pass the image datasets' bilinear Resize(384, max_size=640)
+        before the processor, as the reference's datasets do (cocoimages_dataset_crossvqas.py:83,108-109; on the device,
+        image_processing.DatasetResize).  Off by default: images reach the processor as they are given.
+        image_size: the engine's static pixel frame, an int (square) or (height, width).
         max_patches: patch slots per sample instead of one sequence position per cell of the frame (ViltBackbone): with
         image_size=(640, 640), max_patches=240 one engine takes every image the ViLT size rule yields, portrait and landscape.
         num_labels: width of every task head (task_configs_fed.py: 100 for the CLOVE / domain tasks, 3129 for vqa; one engine
@@ -231,6 +235,7 @@ class ViltContinualLearner:
         self._vocab = vocab
         self._tokenizer = None
         self._image_processor = None
+        self.dataset_resize, self._dataset_resize = bool(dataset_resize), None
         self.gating = False
         self.active = "adapter_1" if optimizer_mode == "dat" else "adapter" if optimizer_mode == "adapter" else None
         # requires_grad flags per adapter, toggled exactly like adapter.py:66-95; prepare_model's initial state
@@ -319,16 +324,25 @@ class ViltContinualLearner:
         if len(arrs) != len(texts):
             raise L.FeddatHipError(f"{len(arrs)} images but {len(texts)} texts")
         eng = self.engine
+        stage1 = None
+        if self.dataset_resize:      # the datasets' Resize first: the slot budget below and the processor's frame check see
+            from .image_processing import DatasetResize, decoded_images      # the sizes it leaves
+            if self._dataset_resize is None:
+                self._dataset_resize = DatasetResize(self.device)
+            stage1, arrs = self._dataset_resize, decoded_images(arrs)
+            sizes = [stage1.output_size(a.shape[0], a.shape[1], larger_only=True) for a in arrs]
         if eng.max_patches is not None:      # the slot budget, from the sizes alone (before any image is resized)
             from .image_processing import resize_output_size
             for i, a in enumerate(arrs):
                 shp = a.shape if hasattr(a, "shape") else None
+                if stage1 is not None:
+                    shp = sizes[i] + (3,)
                 if shp is not None and len(shp) == 3:
                     oh, ow = resize_output_size(int(shp[0]), int(shp[1]))
                     if (oh // eng.P) * (ow // eng.P) > eng.max_patches:
                         raise L.FeddatHipError(f"image {i} ({shp[0]}x{shp[1]}) resizes to {oh}x{ow}: {(oh // eng.P) * (ow // eng.P)} "
                                                f"patches, the engine was built with max_patches = {eng.max_patches}")
-        enc = dict(self.image_processor(arrs))
+        enc = dict(self.image_processor(arrs if stage1 is None else stage1(arrs, larger_only=True)))
         tok = self.tokenizer(list(texts), padding="max_length", truncation=True, max_length=self.max_text_length)
         enc.update(input_ids=tok["input_ids"], attention_mask=tok["attention_mask"], token_type_ids=tok["token_type_ids"])
         return enc
@@ -348,12 +362,13 @@ def create_vilt_continual_learner_model(params: Dict[str, torch.Tensor], ordered
                                         batch_size: int, image_size=384, num_layers: int = 12,
                                         lr: float = 1e-4, vocab=None, operands: str = None,
                                         optimizer_mode: str = "dat", num_labels: int = 100,
-                                        max_patches: Optional[int] = None) -> ViltContinualLearner:
+                                        max_patches: Optional[int] = None,
+                                        dataset_resize: bool = False) -> ViltContinualLearner:
     """vilt.py:421-452 (the pretrained checkpoint is passed in as a tensor dict: feddat_amd.weights.load_vilt_pretrained
     reads it from a local HF directory; there is no hub access here)."""
     return ViltContinualLearner(ordered_cl_tasks, params, device, batch_size, image_size, num_layers, lr, vocab=vocab,
                                 operands=operands, optimizer_mode=optimizer_mode, num_labels=num_labels,
-                                max_patches=max_patches)
+                                max_patches=max_patches, dataset_resize=dataset_resize)
 
 
 def convert_batch_to_vilt_input_dict(batch: Dict):

@@ -223,7 +223,8 @@ class AlbefTaskTrainer(TaskTrainer):
         if isinstance(batch, (list, tuple)):           # the reference's collated list (albef.py:275-286)
             from .albef_modeling import convert_batch_to_albef_input_dict
             batch = convert_batch_to_albef_input_dict(batch)
-        if "questions" in batch:                       # strings -> device tokenizer, once per batch (task_trainer.py:250-264)
+        # strings -> device tokenizer, image lists -> device image transform, once per batch (task_trainer.py:250-264)
+        if "questions" in batch or model.image_list(batch) is not None:
             batch = model.process_inputs(dict(batch, train=True))
         out = model.engine.train_step(batch, use_graph=self.use_graph)
         model.activate_gating()
@@ -338,6 +339,10 @@ def build_parser() -> argparse.ArgumentParser:
                    help="ALBEF with --synthetic_answer_list: evaluation questions per client, in batches of min(val_batch_size, "
                         "batch_size) with a short last one (drop_last=False: vqa_dataset_crossvqa.py:580-603).  Default "
                         "batch_size + 1")
+    p.add_argument("--synthetic_raw_images", action="store_true",
+                   help="ALBEF: every synthetic training and evaluation batch carries seeded decoded uint8 images of mixed sizes and "
+                        "orientations (albef_spec.synthetic_raw_images) instead of N(0,1) tensors; the reference's image transform "
+                        "(dataset Resize, bicubic Resize, ToTensor, Normalize) runs on the device once per batch")
     p.add_argument("--image_size", type=int, default=384)
     p.add_argument("--image_frame", type=str, default=None,
                    help="ViLT: H,W of the engine's pixel frame (multiples of 32) instead of the square --image_size frame, e.g. "
@@ -432,6 +437,9 @@ def main(argv=None):
             if text_len + 1 + args.max_image_patches > 320:
                 raise L.FeddatHipError(f"--max_image_patches {args.max_image_patches} makes sequences of "
                                        f"{text_len + 1 + args.max_image_patches} tokens; the attention kernels take at most 320")
+    if args.synthetic_raw_images and "albef" not in args.encoder_name:
+        raise L.FeddatHipError("--synthetic_raw_images is an ALBEF option (--encoder_name albef_no_distill); ViLT takes decoded images "
+                               "through ViltContinualLearner(..., dataset_resize=True).forward(task_key, images, texts)")
     if args.synthetic_answer_list < 0:
         raise L.FeddatHipError(f"--synthetic_answer_list must be >= 0, got {args.synthetic_answer_list}")
     if args.synthetic_answer_list and "albef" not in args.encoder_name:
@@ -515,8 +523,11 @@ def main(argv=None):
     personal_params = {t: personal(model.state_dict()) for t in my_tasks}
     def make_batch(seed, ti=0, n=None):
         if albef:
-            return albef_spec.synthetic_batch(args.batch_size, seed, image=args.image_size, vocab=dims.get("vocab", 30522),
-                                              device=dev)
+            b = albef_spec.synthetic_batch(args.batch_size, seed, image=args.image_size, vocab=dims.get("vocab", 30522),
+                                           device=dev)
+            if args.synthetic_raw_images:
+                b["image"] = albef_spec.synthetic_raw_images(args.batch_size, seed, image=args.image_size)
+            return b
         prior = vilt_spec.client_label_prior(ti, num_labels, alpha=args.synthetic_label_alpha) \
             if args.synthetic_label_alpha > 0 else None
         if args.synthetic_orientations:
@@ -542,6 +553,11 @@ def main(argv=None):
                                                          a_mask, min(64, M), image=args.image_size, q_len=eng.Lq, vocab=vocab,
                                                          device=dev)      # k: task_trainer.py:172
                      for ti, t in enumerate(tasks) if t in my_tasks}
+        if args.synthetic_raw_images:
+            for ti, t in enumerate(tasks):
+                for s, b in enumerate(eval_data.get(t, [])):
+                    b["image"] = albef_spec.synthetic_raw_images(b["question_ids"].shape[0], args.seed + 600000 + 1000 * ti + s,
+                                                                 image=args.image_size)
     # {round: {client: scores}} of the periodic evaluation, and what it ran on: kept on the returned model
     model.eval_scores, model.eval_data, model.personal_params = {}, eval_data, personal_params
     server_flat = eng.comm_flat().clone()

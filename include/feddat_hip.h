@@ -790,6 +790,32 @@ int feddat_vilt_image_preprocess(const uint8_t* images, const long* offsets, con
                                  const int* out_h, const int* out_w, int n, int Hm, int Wm, float* pixel_values,
                                  long* pixel_mask, void* workspace, long workspace_bytes, hipStream_t stream);
 
+/* Additions within ABI 8: the two stages of the reference's image transform that come before / beside the processor above, on
+ * the same resample machinery (Pillow's 8-bit ImagingResample, bit for bit).  Filter selectors = Pillow's enum values. */
+#define FEDDAT_FILTER_BILINEAR 2 /* Image.BILINEAR: triangle 1 - |x|, support 1 */
+#define FEDDAT_FILTER_BICUBIC 3  /* Image.BICUBIC: a = -0.5, support 2 */
+/* Stage 1, the image datasets' torchvision Resize(384, max_size=640) on the PIL image (cocoimages_dataset_crossvqas.py:83,
+ * 108-109; BILINEAR): n packed [h][w][3] uint8 images at images + offsets[i] -> n packed [out_h][out_w][3] uint8 images at
+ * out + out_offsets[i], either filter, per-image sizes, up- or down-scale (out_* = feddat_amd.image_processing.
+ * dataset_resize_size for the reference's rule).  An axis whose size does not change keeps its bytes.  Host arrays as above;
+ * images / out are device memory and may be two regions of one allocation as long as no result overlaps a source or another
+ * result (not checked).  The result feeds feddat_vilt_image_preprocess or feddat_albef_image_preprocess as their `images`.
+ * workspace: feddat_image_resample_workspace_bytes(...) bytes (-1: a size <= 0 or an unknown filter). */
+long feddat_image_resample_workspace_bytes(const int* heights, const int* widths, const int* out_h, const int* out_w, int n,
+                                           int filter);
+int feddat_image_resample_u8(const uint8_t* images, const long* offsets, const int* heights, const int* widths,
+                             const int* out_h, const int* out_w, const long* out_offsets, int n, int filter, uint8_t* out,
+                             void* workspace, long workspace_bytes, hipStream_t stream);
+/* Stage 2 for ALBEF, the VQA dataset's transform (vqa_dataset_crossvqa.py:533-572): Resize((R, R), BICUBIC), ToTensor,
+ * Normalize(mean, std).  n packed uint8 images (as above) -> out fp32 [n,3,R,R]: out[i][c][y][x] = (float(r) / 255.0f -
+ * mean[c]) / std[c] in IEEE float32 (division, not a reciprocal product), r = the resized byte.  mean / std: HOST float[3]
+ * (they reach the kernel by value); std[c] != 0.  out is written in place with no padding and no mask, so it may be the
+ * engine's own static image buffer or the first n samples of it. */
+long feddat_albef_image_workspace_bytes(const int* heights, const int* widths, int n, int R);
+int feddat_albef_image_preprocess(const uint8_t* images, const long* offsets, const int* heights, const int* widths, int n,
+                                  int R, const float* mean, const float* std, float* out, void* workspace,
+                                  long workspace_bytes, hipStream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Input pipeline, text half: BERT WordPiece tokenisation as the reference obtains it from
  * ViltProcessor(text=..., padding=True, truncation=True, max_length=40) (src/modeling/vilt.py:98) and
