@@ -38,7 +38,7 @@ def build(force: bool = False, verbose: bool = False, ablate: bool = False, f16:
     variant / extra_flags: an experimental build of either (tools/ A/Bs, e.g. variant="nt", extra_flags=["-DFD_EPI_NT"]) ->
     libfeddat_hip[_f16]_<variant>.so in its own object directory; nothing in feddat_amd/ loads such a library."""
     srcs = sorted(glob.glob(os.path.join(CSRC, "*.hip")))
-    hdrs = sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(ROOT, "include", "feddat_hip.h")]
+    hdrs = sorted(glob.glob(os.path.join(CSRC, "*.h"))) + sorted(glob.glob(os.path.join(ROOT, "include", "*.h")))
     objdir = os.path.join(PKG, "build_ablate" if ablate else "build_f16" if f16 else "build")
     LIB = ABLATE_LIB if ablate else F16_LIB if f16 else globals()["LIB"]
     FLAGS = globals()["FLAGS"] + (["-DFEDDAT_ABLATE"] if ablate else []) + (["-DFEDDAT_OPERANDS_F16"] if f16 else [])

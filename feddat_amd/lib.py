@@ -1,4 +1,4 @@
-"""ctypes binding of libfeddat_hip.so (include/feddat_hip.h).
+"""ctypes binding of libfeddat_hip.so (include/feddat_hip.h and its extension header include/feddat_hip_prompt.h).
 
 The HIP library is THE product path: if it cannot be loaded this module raises -- there is no eager /
 PyTorch / CPU fallback anywhere in feddat_amd.  torch is used only as plumbing: device allocations
@@ -225,6 +225,13 @@ _SIGS = {
 
 EXPORTED_SYMBOLS = tuple(_SIGS.keys())
 
+# the extension header include/feddat_hip_prompt.h (csrc/prompt.hip): the same libraries, their own table
+_PROMPT_SIGS = {
+    "feddat_prompt_frame_assemble": [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],
+    "feddat_prompt_grad_gather": [vp, i32, i32, i32, i32, f32, vp, vp, vp, vp],
+}
+PROMPT_SYMBOLS = tuple(_PROMPT_SIGS.keys())
+
 
 class FeddatHipError(RuntimeError):
     pass
@@ -241,7 +248,7 @@ def _open(path: str, want_format: int) -> C.CDLL:
             f"{path} not found: the HIP library is the only implementation of this path "
             "(no CPU/PyTorch fallback). Build it with `python __graft_entry__.py` or `python -m feddat_amd.build`.")
     lib = C.CDLL(path)
-    for name, args in _SIGS.items():
+    for name, args in list(_SIGS.items()) + list(_PROMPT_SIGS.items()):
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = i64 if name.endswith(("_workspace_elems", "_workspace_bytes", "_table_entries")) else i32
@@ -924,6 +931,70 @@ def vector_grad_reduce(table, njobs, max_n, unscale=1.0, unscale_dev=None, nonfi
     assert nonfinite is None or nonfinite.dtype == torch.int32
     _chk(load().feddat_vector_grad_reduce(_p(table), njobs, max_n, unscale, _p(unscale_dev), _p(nonfinite), _stream()),
          "feddat_vector_grad_reduce")
+
+
+# ---- prompt tuning (optimizer_mode prompt; include/feddat_hip_prompt.h, csrc/prompt.hip)
+PROMPT_ROWS = 5      # rows per insertion point: the reference's prompt_tokens = arange(5)
+
+
+def prompt_row_map(Lt: int, Np: int):
+    """Pure host function: the source of every row of the prompted frame of S = Lt + 1 + Np + 10 rows, as
+    feddat_prompt_frame_assemble lays it out: ("src", r) = row r of the unprompted [text(Lt) | CLS | patches(Np)] frame,
+    ("prompt", j, m) = P[j] + modality[m]."""
+    n = PROMPT_ROWS
+    if Lt < 1 or Np < 1:
+        raise FeddatHipError(f"a prompted frame needs at least one text token and one patch, got Lt = {Lt}, Np = {Np}")
+    rows = [("src", 0)] + [("prompt", j, 0) for j in range(n)] + [("src", r) for r in range(1, Lt + 1)]
+    rows += [("prompt", j, 1) for j in range(n)] + [("src", r) for r in range(Lt + 1, Lt + 1 + Np)]
+    return rows
+
+
+def prompt_frame_assemble(h_in, key_mask_in, P, mod0, mod1, h_out, key_mask_out, B, Lt, Np, H, nrep=1):
+    """h_in fp32 [B, Lt + 1 + Np, H] + the five prompt rows P [5, H] -> h_out fp32 [B, Lt + 1 + Np + 10, H] and, when
+    key_mask_out (uint8 [nrep * B, S]) is given, its key mask from key_mask_in (uint8, row stride Lt + 1 + Np)."""
+    _dev(h_in, key_mask_in, P, mod0, mod1, h_out, key_mask_out)
+    S0 = Lt + 1 + Np
+    assert h_in.dtype == h_out.dtype == P.dtype == torch.float32 and h_in.is_contiguous() and h_out.is_contiguous()
+    assert h_in.numel() >= B * S0 * H and h_out.numel() >= B * (S0 + 2 * PROMPT_ROWS) * H and P.numel() >= PROMPT_ROWS * H
+    assert P.is_contiguous() and mod0.numel() >= H and mod1.numel() >= H
+    if key_mask_out is not None:
+        assert key_mask_in.dtype == key_mask_out.dtype == torch.uint8 and key_mask_in.is_contiguous()
+        assert key_mask_out.is_contiguous() and key_mask_in.numel() >= B * S0
+        assert key_mask_out.numel() >= nrep * B * (S0 + 2 * PROMPT_ROWS)
+    _chk(load().feddat_prompt_frame_assemble(_p(h_in), _p(key_mask_in), _p(P), _p(mod0), _p(mod1), _p(h_out), _p(key_mask_out),
+                                             B, Lt, Np, H, nrep, _stream()), "feddat_prompt_frame_assemble")
+
+
+def prompt_grad_gather(dh0, B, S, Lt, H, G, unscale=1.0, unscale_dev=None, nonfinite=None):
+    """G [5, H] = sum over the samples of the ten prompt rows' gradient in dh0 fp32 [B, S, H] (text row, then image row, b
+    ascending), times unscale * unscale_dev[0]; nonfinite (int32 device tensor, optional) gets 1 OR-ed in on an inf / NaN."""
+    _dev(dh0, G, unscale_dev, nonfinite)
+    assert dh0.dtype == G.dtype == torch.float32 and dh0.is_contiguous() and G.is_contiguous()
+    assert dh0.numel() >= B * S * H and G.numel() >= PROMPT_ROWS * H
+    assert nonfinite is None or nonfinite.dtype == torch.int32
+    _chk(load().feddat_prompt_grad_gather(_p(dh0), B, S, Lt, H, unscale, _p(unscale_dev), _p(G), _p(nonfinite), _stream()),
+         "feddat_prompt_grad_gather")
+
+
+def prompt_mlp_fwd(E, W1, b1, W2, b2, t, P):
+    """The reference's prompt MLP on its five tokens, two dependent feddat_head_gemm launches: t = tanh(E W1^T + b1) [5, D]
+    (kept for the backward), P = t W2^T + b2 [5, H].  E [5, H], W1 [D, H], W2 [H, D]."""
+    n, H = E.shape
+    D = W1.shape[0]
+    head_gemm(ht_job(E, H, 1, W1, 1, H, n, D, H, t, bias_j=b1, epi=HT_EPI_TANH))
+    head_gemm(ht_job(t, D, 1, W2, 1, D, n, H, D, P, bias_j=b2))
+
+
+def prompt_mlp_bwd(G, t, E, W1, W2, dt, dE, dW1, db1, dW2, db2):
+    """Backward of prompt_mlp_fwd from G = dL/dP [5, H], two feddat_head_gemm launches of two independent products each:
+    {dW2 = G^T t with db2 = column sums of G; dt = G W2}, then with dz = dt * (1 - t^2) formed in the operand prologue
+    {dW1 = dz^T E with db1 = column sums of dz; dE = dz W1}.  The outputs may be slices of a flat gradient buffer."""
+    n, H = E.shape
+    D = W1.shape[0]
+    head_gemm(ht_job(G, 1, H, t, D, 1, H, D, n, dW2, mode=1, colsum=db2),
+              ht_job(G, H, 1, W2, D, 1, n, D, H, dt))
+    head_gemm(ht_job(dt, 1, D, E, H, 1, D, H, n, dW1, mode=1, colsum=db1, pro=HT_PRO_TANH_BWD, pro_a=t),
+              ht_job(dt, D, 1, W1, H, 1, n, H, D, dE, pro=HT_PRO_TANH_BWD, pro_a=t))
 
 
 def single_step_finish(states, flag, scaler_f, scaler_i, growth=2.0, backoff=0.5, growth_interval=2000):

@@ -18,7 +18,7 @@ import torch
 
 from . import lib as L
 from .engine import ViltDatEngine, ENC
-from .modes import MODES, VECTOR_MODES, mode_names
+from .modes import MODES, PROMPT_MODE, VECTOR_MODES, mode_names
 
 
 class _Param:
@@ -211,8 +211,9 @@ class ViltContinualLearner:
         accelerate_config.yaml:8) or "bf16" (engine.ViltDatEngine).
         optimizer_mode: "dat" (adapter_{0,1,2}, engine.ViltDatEngine) or "adapter" (the FedAvg baseline: one adapter per
         layer, adapter_engine.ViltAdapterEngine; main.py:114-118,141-149), "bias" or "norm" (the plain backbone with every
-        'bias' / 'norm' parameter trainable, vector_engine.ViltVectorEngine; main.py:176-196).  state_dict() holds the trainable
-        tensors under the reference's keys; bias / norm add no parameters."""
+        'bias' / 'norm' parameter trainable, vector_engine.ViltVectorEngine; main.py:176-196), or "prompt" (the plain backbone
+        with the reference's two prompt modules, prompt_engine.ViltPromptEngine; main.py:198-245).  state_dict() holds the
+        trainable tensors under the reference's keys; bias / norm add no parameters."""
         self.ordered_cl_tasks = list(ordered_cl_tasks)
         self.device = torch.device(device)
         self.optimizer_mode = optimizer_mode
@@ -225,8 +226,11 @@ class ViltContinualLearner:
             import functools
             from .vector_engine import ViltVectorEngine
             Engine = functools.partial(ViltVectorEngine, mode=optimizer_mode)
+        elif optimizer_mode == PROMPT_MODE:
+            from .prompt_engine import ViltPromptEngine
+            Engine = ViltPromptEngine
         else:
-            raise L.FeddatHipError(f"optimizer_mode must be one of {MODES}, got {optimizer_mode!r}")
+            raise L.FeddatHipError(f"optimizer_mode must be one of {MODES + (PROMPT_MODE,)}, got {optimizer_mode!r}")
         self.engine = Engine(params, self.ordered_cl_tasks, self.device, batch=batch_size, res=image_size, layers=num_layers,
                              lr=lr, operands=operands, num_labels=num_labels,
                              **({} if max_patches is None else {"max_patches": max_patches}))
@@ -248,7 +252,7 @@ class ViltContinualLearner:
 
     # ---- adapter switches (vilt.py:363-373) ----
     def set_active_adapter(self, name):
-        if self.optimizer_mode in VECTOR_MODES:
+        if self.optimizer_mode in VECTOR_MODES + (PROMPT_MODE,):
             raise L.FeddatHipError(f"optimizer_mode {self.optimizer_mode} has no adapter (got {name!r})")
         if self.optimizer_mode == "adapter":
             if name != "adapter":
@@ -270,7 +274,7 @@ class ViltContinualLearner:
         """Which adapters a freshly created optimizer would hold (create_optimizer filters on requires_grad)."""
         if self.optimizer_mode == "adapter":
             return (0,)
-        if self.optimizer_mode in VECTOR_MODES:      # no adapter: the optimizer holds the mode's vectors and the head
+        if self.optimizer_mode in VECTOR_MODES + (PROMPT_MODE,):      # no adapter: the optimizer holds the mode's tensors and the head
             return ()
         return tuple(a for a in (0, 1) if self.adapter_requires_grad[a])
 
@@ -350,7 +354,7 @@ class ViltContinualLearner:
     def forward(self, task_key: str, images, texts=None):
         if not isinstance(images, dict):
             images = self.process_inputs(images, texts)
-        if self.optimizer_mode == "adapter" or self.optimizer_mode in VECTOR_MODES:
+        if self.optimizer_mode == "adapter" or self.optimizer_mode in VECTOR_MODES + (PROMPT_MODE,):
             return self.engine.forward(images, task_key)
         mode = "gating" if self.gating else self.active
         return self.engine.forward(images, mode, task_key)

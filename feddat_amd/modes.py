@@ -10,6 +10,13 @@ module does the same on the keys it is given.
   adapter    adapter, heads                 every 'adapter' key       heads ('task')
   bias       every 'bias' key, heads        every 'bias' key          heads ('task')
   norm       every 'norm' key, heads        every 'norm' key          heads ('task')
+  prompt     every 'prompt' key, heads      every 'prompt' key        heads ('task')
+
+prompt (main.py:198-245): embeddings.prompt_embedding_{vis,text}.{0.weight, 1.weight, 1.bias, 3.weight, 3.bias}, 299 712 floats
+per module, 599 424 communicated.  The forward reads the text module on both sides of the sequence (prompted_output.py:254), so
+the vis tensors are trainable by name but never get a gradient: AdamW skips them and they travel unchanged.  No 'prompt' key
+contains 'clf'.  prompt_engine.ViltPromptEngine runs the mode; the command line (train.main) does not offer it yet, which is why
+it is PROMPT_MODE beside MODES and not a fifth entry of it.
 
 bias (BitFit): per layer query|key|value.bias, attention.output.dense.bias, intermediate.dense.bias, output.dense.bias (the HF key: no Adaptered_ViltOutput here),
 layernorm_before.bias, layernorm_after.bias (8 448 floats), once text_embeddings.LayerNorm.bias,
@@ -37,19 +44,21 @@ from . import lib as L
 MODES = ("dat", "adapter", "bias", "norm")
 # the modes whose trainable backbone tensors are per-column vectors (vector_engine.ViltVectorEngine)
 VECTOR_MODES = ("bias", "norm")
+# prompt tuning (prompt_engine.ViltPromptEngine): known to mode_names / averaged_names and the Python surface, not to train.main
+PROMPT_MODE = "prompt"
 
 
 def mode_names(keys: Sequence[str], mode: str) -> Dict[str, List[str]]:
     """{"trainable", "communicated", "personal"}: the subsets of `keys` (state-dict order kept) for optimizer_mode `mode`."""
-    if mode not in MODES:
-        raise L.FeddatHipError(f"optimizer_mode must be one of {MODES}, got {mode!r}")
+    if mode not in MODES + (PROMPT_MODE,):
+        raise L.FeddatHipError(f"optimizer_mode must be one of {MODES + (PROMPT_MODE,)}, got {mode!r}")
     keys = list(keys)
     if mode == "dat":
         # '.cls.': the ALBEF decoder's LM head (main.py:127-128,247-250); no ViLT key contains it
         return dict(trainable=[k for k in keys if "task" in k or ".cls." in k or "adapter_0" in k or "adapter_1" in k],
                     communicated=[k for k in keys if "adapter_1" in k],
                     personal=[k for k in keys if "task" in k or ".cls." in k or "adapter_0" in k or "adapter_2" in k])
-    sub = mode          # "adapter" | "bias" | "norm": the substring main.py matches is the mode's own name
+    sub = mode          # "adapter" | "bias" | "norm" | "prompt": the substring main.py matches is the mode's own name
     return dict(trainable=[k for k in keys if sub in k or "task" in k],
                 communicated=[k for k in keys if sub in k],
                 personal=[k for k in keys if "task" in k])

@@ -26,7 +26,7 @@ from . import lib as L
 from . import vilt_spec
 from .fedavg import all_reduce_sum, allreduce_average, get_average_net  # noqa: F401  (re-exported: main.py:50)
 from .modeling import ViltContinualLearner, convert_batch_to_vilt_input_dict, create_vilt_continual_learner_model
-from .modes import MODES, VECTOR_MODES, mode_names
+from .modes import MODES, PROMPT_MODE, VECTOR_MODES, mode_names
 
 
 class OptimizerHandle:
@@ -160,9 +160,9 @@ class TaskTrainer:
         switches the reference performs inside (activate_gating / set_active_adapter, task_trainer.py:284-312)
         leave the model in the same final state: gating on, adapter_0 active.
         optimizer_mode adapter: one forward / backward / AdamW step / scheduler tick (task_trainer.py:433-450); returns
-        loss = BCE * num_labels.  optimizer_mode bias / norm: the same step on the adapter-less model."""
+        loss = BCE * num_labels.  optimizer_mode bias / norm / prompt: the same step on the adapter-less model."""
         out = model.engine.train_step(self.encode_batch(model, batch), use_graph=self.use_graph)
-        if self._mode(model) == "adapter" or self._mode(model) in VECTOR_MODES:
+        if self._mode(model) == "adapter" or self._mode(model) in VECTOR_MODES + (PROMPT_MODE,):
             return out[0]
         model.activate_gating()
         model.set_active_adapter("adapter_0")
@@ -183,7 +183,7 @@ class TaskTrainer:
 
     def eval(self, model: ViltContinualLearner):
         loader = self.vqa_test_dataloader
-        if self._mode(model) in VECTOR_MODES:      # no adapter to switch: one score
+        if self._mode(model) in VECTOR_MODES + (PROMPT_MODE,):      # no adapter to switch: one score
             return self.eval_one_loader(model, loader)
         if self._mode(model) == "adapter":      # task_trainer.py:232-233,246: one score
             model.set_active_adapter("adapter")
@@ -401,6 +401,8 @@ def federation_num_labels(tasks: Sequence[str]) -> int:
 def main(argv=None):
     args = build_parser().parse_args(argv)
     mode = "dat" if "dat" in args.optimizer_mode else args.optimizer_mode
+    # the command line's own four names: modes.mode_names and the Python surface also know PROMPT_MODE, which main does not
+    # offer yet
     if mode not in MODES:
         raise L.FeddatHipError("--optimizer_mode dat, adapter, bias or norm are on the MI355X hot path (SURVEY.md section 2, "
                                "row 13)")

@@ -65,6 +65,34 @@ def vector_names(mode: str, layers: int, hidden: int = 768, inter: int = 3072) -
     return out
 
 
+def alloc_kept_layers(eng: ViltBackbone) -> List[dict]:
+    """The activations an adapter-less engine keeps for its backward: every layer at R rows, layer 0 included; no adapter
+    between the layers, so layer i reads layer i - 1's output in place (shared with prompt_engine.ViltPromptEngine)."""
+    act: List[dict] = []
+    for i in range(eng.nl):
+        act.append(eng._kept_layer(h_in=eng.h0 if i == 0 else act[i - 1]["h3"]))
+    return act
+
+
+def forward_kept_layers(eng: ViltBackbone):
+    """Behind the embeddings (eng.h0, eng.key_mask2): layers 0 .. L-2 at R rows (activations kept in eng.act), the top layer on
+    its token-0 rows, LayerNorm + pooler (shared with prompt_engine.ViltPromptEngine)."""
+    R, B, H = eng.R, eng.B, eng.H
+    m1 = eng.key_mask2[:B]
+    top = eng.nl - 1
+    for i in range(top):
+        a = eng.act[i]
+        eng._layer_body(i, a["h_in"], R, B, a["qkv"], a["ctx"], a["lse"], a["h2"], a["h3"], st1=a["st1"], st2=a["st2"],
+                        u=a["u"], mask=m1, ln1_done=False)
+    a, W, t = eng.act[top], eng.layers[top], eng.top
+    x16 = eng.x16[:R]
+    L.layernorm_fwd(a["h_in"], W["ln1g"], W["ln1b"], eng.ln_eps, R, H, y_bf16=x16, stats=a["st1"])
+    L.gemm_bf16_nt(x16, W["wqkv"], L.EPI_BF16, bias=W["bqkv"], out_bf16=a["qkv"])
+    L.attn_cls_fwd(a["qkv"], a["ctx"], a["lse"], B, eng.S, eng.heads, key_mask=m1)
+    eng._top_token0_fwd(a, W, B)
+    eng._pool(t["h3"], B, x_stride=H)
+
+
 class ViltVectorEngine(ViltBackbone):
     def __init__(self, params: Dict[str, torch.Tensor], tasks: Sequence[str], device, batch: int, res: int, mode: str = "bias",
                  fp8: bool = False, **kw):
@@ -111,9 +139,7 @@ class ViltVectorEngine(ViltBackbone):
             self.lnf_g = v(ENC + "layernorm.weight")
         # ---------------- activations kept for the backward: every layer at R rows, layer 0 included; no adapter between the
         # layers, so layer i reads layer i - 1's output in place
-        self.act: List[dict] = []
-        for i in range(nl):
-            self.act.append(self._kept_layer(h_in=self.h0 if i == 0 else self.act[i - 1]["h3"]))
+        self.act: List[dict] = alloc_kept_layers(self)
         # static row masks of h0's [text | cls | patches] rows
         s = torch.arange(self.S, device=dev).repeat(B)
         self.text_rows = (s < self.Lt).to(torch.uint8).contiguous()
@@ -171,21 +197,8 @@ class ViltVectorEngine(ViltBackbone):
     # ------------------------------------------------------------------------------------------ forward
     def _forward_plain(self):
         """Embeddings, layers 0 .. L-2 at R rows (activations kept), the top layer on its token-0 rows, LayerNorm + pooler."""
-        R, B, H = self.R, self.B, self.H
-        m1 = self.key_mask2[:B]
         self._embed()
-        top = self.nl - 1
-        for i in range(top):
-            a = self.act[i]
-            self._layer_body(i, a["h_in"], R, B, a["qkv"], a["ctx"], a["lse"], a["h2"], a["h3"], st1=a["st1"], st2=a["st2"],
-                             u=a["u"], mask=m1, ln1_done=False)
-        a, W, t = self.act[top], self.layers[top], self.top
-        x16 = self.x16[:R]
-        L.layernorm_fwd(a["h_in"], W["ln1g"], W["ln1b"], self.ln_eps, R, H, y_bf16=x16, stats=a["st1"])
-        L.gemm_bf16_nt(x16, W["wqkv"], L.EPI_BF16, bias=W["bqkv"], out_bf16=a["qkv"])
-        L.attn_cls_fwd(a["qkv"], a["ctx"], a["lse"], B, self.S, self.heads, key_mask=m1)
-        self._top_token0_fwd(a, W, B)
-        self._pool(t["h3"], B, x_stride=H)
+        forward_kept_layers(self)
 
     # ------------------------------------------------------------------------------------------ backward
     def _backward_plain(self):

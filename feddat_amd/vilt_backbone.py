@@ -1,7 +1,7 @@
 """The frozen ViLT-B/32 backbone and the task head, as every ViLT local-update engine uses them on MI355X.
 
-What the dual-adapter engine (engine.ViltDatEngine), the single-adapter engine (adapter_engine.ViltAdapterEngine) and the bias /
-LayerNorm-only engine (vector_engine.ViltVectorEngine) share INSIDE a train_step: the geometry, the frozen weights as 16-bit MFMA
+What the dual-adapter engine (engine.ViltDatEngine), the single-adapter engine (adapter_engine.ViltAdapterEngine), the bias /
+LayerNorm-only engine (vector_engine.ViltVectorEngine) and the prompt engine (prompt_engine.ViltPromptEngine) share INSIDE a train_step: the geometry, the frozen weights as 16-bit MFMA
 operands (+ transposes for the dX products), the task heads, the static input buffers, the embeddings, the body of one HF ViltLayer,
 the token-0 block of the top layer, LayerNorm + pooler, the head's forward / backward, and the workspace all of this runs on.
 What they share AROUND the step is local_update.LocalUpdateEngine.  An engine derived from ViltBackbone adds its own trainable
@@ -37,7 +37,7 @@ class ViltBackbone(LocalUpdateEngine):
                  text_len: int = 40, layers: int = 12, num_labels: int = 100, lr: float = 1e-4,
                  weight_decay: float = 1e-2, adam_eps: float = 1e-8, gelu_codes: bool = True, operands: Optional[str] = None,
                  loss_scale: Optional[float] = None, dynamic_loss_scale: Optional[bool] = None,
-                 scale_growth_interval: int = 2000, max_patches: Optional[int] = None):
+                 scale_growth_interval: int = 2000, max_patches: Optional[int] = None, extra_tokens: int = 0):
         """operands ("f16", the default, or "bf16"), loss_scale, dynamic_loss_scale, scale_growth_interval and gelu_codes: see
         engine.ViltDatEngine.
         max_patches (None: the grid frame, every cell of the res frame is a sequence position): the image half of the sequence
@@ -45,10 +45,12 @@ class ViltBackbone(LocalUpdateEngine):
         compacted into its slots in row-major order, as HF visual_embed does with max_image_length = -1, so a frame that holds
         portrait and landscape images (res up to 640 x 640) runs at the longest image's patch count (240).  A sample with more
         valid patches than slots raises FeddatHipError: in set_batch for a host pixel_mask, at the end-of-update check
-        (assert_finite) for a device-resident one."""
+        (assert_finite) for a device-resident one.
+        extra_tokens (0: none): rows per sample that the engine itself inserts into the sequence behind the embeddings (prompt
+        tuning: 10), S = text_len + 1 + patches + extra_tokens; self.S0 stays the embeddings' own row count."""
         self._init_loss_scale(operands or "f16", loss_scale, dynamic_loss_scale, scale_growth_interval)
         self._init_backbone(params, tasks, device, batch, res, text_len, layers, num_labels, lr, weight_decay, adam_eps,
-                            gelu_codes, max_patches)
+                            gelu_codes, max_patches, extra_tokens)
 
     def _param(self, params, name):
         return params[name].to(self.dev, torch.float32).contiguous()
@@ -61,7 +63,7 @@ class ViltBackbone(LocalUpdateEngine):
 
     @_bound
     def _init_backbone(self, params, tasks, device, batch, res, text_len, layers, num_labels, lr, weight_decay, adam_eps,
-                       gelu_codes, max_patches=None):
+                       gelu_codes, max_patches=None, extra_tokens=0):
         L.load()
         self.dev = torch.device(device)
         self.tasks = list(tasks)
@@ -84,7 +86,13 @@ class ViltBackbone(LocalUpdateEngine):
             if max(self.gh, self.gw) > 64:
                 raise L.FeddatHipError("a patch-slot frame holds at most 64 x 64 cells")
             self.np = self.max_patches
-        self.S = text_len + 1 + self.np
+        # S0: the rows the embeddings write ([text | CLS | patches]); S: the sequence the layers run on
+        self.extra_tokens = int(extra_tokens)
+        self.S0 = text_len + 1 + self.np
+        self.S = self.S0 + self.extra_tokens
+        if self.extra_tokens < 0 or (self.extra_tokens and self.S > MAX_SEQ):
+            raise L.FeddatHipError(f"extra_tokens = {extra_tokens} makes sequences of {self.S} tokens; the attention kernels "
+                                   f"take at most {MAX_SEQ}")
         self.R = batch * self.S
         self.lr, self.wd, self.eps = lr, weight_decay, adam_eps
         self.ln_eps = 1e-12
@@ -332,31 +340,35 @@ class ViltBackbone(LocalUpdateEngine):
             inp["patch_mask"].fill_(1)
 
     # ------------------------------------------------------------------------------------------ forward
-    def _embed(self):
-        B, H, S, Lt = self.B, self.H, self.S, self.Lt
+    def _embed(self, h=None, key_mask=None):
+        """The embeddings' [text | CLS | patches] rows (S0 per sample) and their key mask, into the sequence frame itself
+        (extra_tokens = 0) or into the staging buffers `h` [B * S0, H] / `key_mask` [NPASS * B, S0] of an engine that inserts rows."""
+        B, H, S, Lt = self.B, self.H, self.S0, self.Lt
+        h = self.h0 if h is None else h
+        key_mask = self.key_mask2 if key_mask is None else key_mask
         e = self.emb
         L.text_embed(self.inp["input_ids"], self.inp["token_type_ids"], e["text_embeddings.word_embeddings.weight"],
                      e["text_embeddings.position_embeddings.weight"], e["text_embeddings.token_type_embeddings.weight"],
                      e["text_embeddings.LayerNorm.weight"], e["text_embeddings.LayerNorm.bias"], self.ln_eps,
-                     self.mod0, self.h0, B, Lt, S, H)
+                     self.mod0, h, B, Lt, S, H)
         # (self.patches was filled by set_batch: im2col of the caller's pixel_values)
         L.gemm_bf16_nt(self.patches, self.w_patch, L.EPI_F32, bias=e["patch_embeddings.projection.bias"],
                        out_f32=self.proj)
         if self.max_patches is not None:      # patch slots: key mask + position value at each slot's cell + assembly + budget check
             L.image_embed_assemble_slots(self.proj, self.cls, self.pos0, self.pos_grid, self.inp["patch_mask"],
-                                         self.inp["attention_mask"], self.mod1, self.h0, self.key_mask2, self.slot_overflow, B,
+                                         self.inp["attention_mask"], self.mod1, h, key_mask, self.slot_overflow, B,
                                          Lt, self.gh, self.gw, self.max_patches, self.g0, H, nrep=self.NPASS)
             return
         if self.fused_tail:      # key mask + per-sample position grid + assembly in one launch (bit-identical)
             L.image_embed_assemble_masked(self.proj, self.cls, self.pos0, self.pos_grid, self.inp["patch_mask"],
-                                          self.inp["attention_mask"], self.mod1, self.h0, self.key_mask2, B, Lt, self.gh,
+                                          self.inp["attention_mask"], self.mod1, h, key_mask, B, Lt, self.gh,
                                           self.gw, self.g0, H, nrep=self.NPASS)
             return
-        L.vilt_key_mask(self.inp["attention_mask"], self.inp["patch_mask"], self.key_mask2, B, Lt, self.gh, self.gw, 1,
+        L.vilt_key_mask(self.inp["attention_mask"], self.inp["patch_mask"], key_mask, B, Lt, self.gh, self.gw, 1,
                         nrep=self.NPASS)
         L.pos_embed_resize_masked(self.pos_grid, self.inp["patch_mask"], self.pos_img, self.g0, B, self.gh, self.gw, 1,
                                   H)
-        L.image_embed_assemble(self.proj, self.cls, self.pos0, self.pos_img, self.mod1, self.h0, B, Lt, self.np, S, H,
+        L.image_embed_assemble(self.proj, self.cls, self.pos0, self.pos_img, self.mod1, h, B, Lt, self.np, S, H,
                                pos_batch_stride=self.np * H)
 
     def _layer_body(self, i: int, h_in, rows: int, nb: int, qkv, ctx, lse, h2, h3, st1=None, st2=None, u=None,

@@ -21,6 +21,29 @@ TASK_NUM_LABELS = {
 }
 
 
+PROMPT_LEN = 5      # main.py:214
+
+
+def prompt_tensor_init(key: str, shape, generator, device="cpu") -> torch.Tensor:
+    """torch's defaults for the modules of a prompt MLP: Embedding N(0, 1); Linear weight and bias U(+-1 / sqrt(fan_in))."""
+    if key.endswith("0.weight"):
+        return torch.randn(shape, generator=generator, device=device)
+    if len(shape) == 2:
+        fan_in = shape[1]
+    else:      # a bias: Linear 1 maps H -> H / 4 (its bias has H / 4 elements), Linear 3 maps H / 4 -> H
+        fan_in = shape[0] * 4 if key.endswith("1.bias") else shape[0] // 4
+    bound = 1.0 / fan_in ** 0.5
+    return (2.0 * torch.rand(shape, generator=generator, device=device) - 1.0) * bound
+
+
+def prompt_init(seed: int = 0, hidden: int = 768, device="cpu") -> Dict[str, torch.Tensor]:
+    """The ten prompt tensors (vis first, state-dict order) drawn by prompt_tensor_init from one generator seeded with `seed`."""
+    g = torch.Generator(device=device)
+    g.manual_seed(seed)
+    shapes = param_shapes(0, (), hidden=hidden, optimizer_mode="prompt")
+    return {k: prompt_tensor_init(k, s, g, device) for k, s in shapes.items() if ".prompt_embedding_" in k}
+
+
 def task_num_labels(task: str) -> int:
     return TASK_NUM_LABELS.get(task, DEFAULT_NUM_LABELS)
 
@@ -29,9 +52,11 @@ def param_shapes(layers: int = 12, tasks: Sequence[str] = ("art",), hidden: int 
                  patch: int = 32, grid: int = 12, max_text: int = 40, vocab: int = 30522, num_labels: int = 100,
                  bottleneck: int = 48, optimizer_mode: str = "dat") -> Dict[str, Tuple[int, ...]]:
     """optimizer_mode "dat": adapter_{0,1,2} in every layer; "adapter": the single `adapter` (main.py:114-118); "bias" / "norm":
-    the plain backbone, no adapter (these modes add no parameters)."""
+    the plain backbone, no adapter (these modes add no parameters); "prompt": the plain backbone with the reference's two prompt
+    modules behind the embeddings' own tensors (main.py:214-229), identical shapes for vis and text."""
     H, I, r = hidden, inter, bottleneck
-    stems = {"dat": ("adapter_0_", "adapter_1_", "adapter_2_"), "adapter": ("adapter_",), "bias": (), "norm": ()}[optimizer_mode]
+    stems = {"dat": ("adapter_0_", "adapter_1_", "adapter_2_"), "adapter": ("adapter_",), "bias": (), "norm": (),
+             "prompt": ()}[optimizer_mode]
     s: Dict[str, Tuple[int, ...]] = {}
     e = ENC + "embeddings."
     s[e + "cls_token"] = (1, 1, H)
@@ -44,6 +69,11 @@ def param_shapes(layers: int = 12, tasks: Sequence[str] = ("art",), hidden: int 
     s[e + "patch_embeddings.projection.weight"] = (H, 3, patch, patch)
     s[e + "patch_embeddings.projection.bias"] = (H,)
     s[e + "token_type_embeddings.weight"] = (3, H)
+    if optimizer_mode == "prompt":      # Sequential(Embedding(5, H), Linear(H, H / 4), Tanh(), Linear(H / 4, H)), vis first
+        for which in ("vis", "text"):
+            p = e + f"prompt_embedding_{which}."
+            s[p + "0.weight"], s[p + "1.weight"], s[p + "1.bias"] = (PROMPT_LEN, H), (H // 4, H), (H // 4,)
+            s[p + "3.weight"], s[p + "3.bias"] = (H, H // 4), (H,)
     for i in range(layers):
         L = ENC + f"encoder.layer.{i}."
         for n in ("query", "key", "value"):
@@ -85,13 +115,16 @@ def random_init(layers: int = 12, tasks: Sequence[str] = ("art",), seed: int = 0
                 num_labels: int = 100) -> Dict[str, torch.Tensor]:
     """BERT-style init (adapter.py:5-14: N(0, 0.02) weights, LayerNorm 1/0) -- biases get a small N(0, bias_std)
     instead of exact zeros so that every bias path of the kernels is exercised.  optimizer_mode "adapter": the single adapter
-    per layer, with init_bert_weights' own zero biases."""
+    per layer, with init_bert_weights' own zero biases.  optimizer_mode "prompt": the prompt modules get torch's own defaults
+    (prompt_tensor_init)."""
     g = torch.Generator(device=device)
     g.manual_seed(seed)
     out = {}
     for k, shp in param_shapes(layers, tasks, num_labels=num_labels, optimizer_mode=optimizer_mode).items():
         is_ln = ("LayerNorm" in k) or ("layernorm" in k) or ("clf_norm0" in k)
-        if optimizer_mode == "adapter" and ".adapter.adapter_" in k and k.endswith("bias"):
+        if ".prompt_embedding_" in k:
+            out[k] = prompt_tensor_init(k, shp, g, device)
+        elif optimizer_mode == "adapter" and ".adapter.adapter_" in k and k.endswith("bias"):
             out[k] = torch.zeros(shp, device=device)
         elif is_ln and k.endswith("weight"):
             out[k] = 1.0 + bias_std * torch.randn(shp, generator=g, device=device)

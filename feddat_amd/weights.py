@@ -95,11 +95,13 @@ def _linear_default(gen, out_f, in_f):
 
 
 def init_trainable(shapes: Dict[str, tuple], seed: int = 0) -> Dict[str, torch.Tensor]:
-    """Fresh adapters and task heads for every such key in `shapes` (the reference builds them at model construction)."""
+    """Fresh adapters, prompt modules and task heads for every such key in `shapes` (the reference builds them at model construction)."""
     gen = torch.Generator().manual_seed(seed)
     out: Dict[str, torch.Tensor] = {}
     for k, shp in shapes.items():
-        if "adapter_" in k:
+        if ".prompt_embedding_" in k:      # absent from a pretrained file: torch's defaults for Embedding / Linear
+            out[k] = vilt_spec.prompt_tensor_init(k, shp, gen)
+        elif "adapter_" in k:
             out[k] = torch.zeros(shp) if k.endswith("bias") else 0.02 * torch.randn(shp, generator=gen)
         elif k.startswith("task_layer.") and k.endswith("clf_norm0.weight"):
             out[k] = torch.ones(shp)
@@ -151,9 +153,9 @@ def convert_vilt_state_dict(sd: Dict[str, torch.Tensor], layers: int = 12) -> Di
 def load_vilt_pretrained(path: str, tasks: Sequence[str], layers: int = 12, seed: int = 0,
                          num_labels: int = 100, optimizer_mode: str = "dat") -> Dict[str, torch.Tensor]:
     """Everything create_vilt_continual_learner_model needs: frozen backbone from `path`, fresh adapters (adapter_{0,1,2}, or
-    the single `adapter` with optimizer_mode "adapter", none with "bias" / "norm") and heads."""
+    the single `adapter` with optimizer_mode "adapter", none with "bias" / "norm", the two prompt modules with "prompt") and heads."""
     sd = convert_vilt_state_dict(read_checkpoint(path), layers)
-    if optimizer_mode in ("bias", "norm"):      # no Adaptered_ViltOutput: the FFN's second product keeps its HF key
+    if optimizer_mode in ("bias", "norm", "prompt"):      # no Adaptered_ViltOutput: the FFN's second product keeps its HF key
         sd = {k.replace(".output.layer.dense.", ".output.dense."): v for k, v in sd.items()}
     shapes = vilt_spec.param_shapes(layers, tasks, num_labels=num_labels, optimizer_mode=optimizer_mode)
     for k, shp in shapes.items():
