@@ -3,7 +3,8 @@
 The reference's non-dat train_step (src/train/visionlanguage_tasks/task_trainer.py:433-450 around src/modeling/vilt.py:244-264
 with adapter_config {"names": ["adapter"]}, main.py:114-118,141-149,248-250): ONE forward through the backbone with one bottleneck
 adapter per layer, loss = BCEWithLogits_mean(logits, target) * C, one backward, one AdamW step over adapter + task head, one
-scheduler tick.  It is the DAT step (engine.ViltDatEngine) with a single pass: the same kernels, the same static-buffer layout at
+scheduler tick.  The step itself is single_pass.SinglePassStep, shared with the bias / norm / prompt engines; forward and backward
+are the dual-adapter engine's (engine.ViltDatEngine) with a single pass: the same kernels, the same static-buffer layout at
 B samples (R = B * S rows) instead of 2 B, the same dynamic loss scale, and one hipGraph per step.  The adapter's tensors are
 `...output.adapter.adapter_{down,up}.{weight,bias}`; the FedAvg payload (comm_flat) is all of them, back-to-back.
 """
@@ -15,10 +16,10 @@ import torch
 
 from . import lib as L
 from .engine import ViltDatEngine
-from .local_update import _bound
+from .single_pass import SinglePassStep
 
 
-class ViltAdapterEngine(ViltDatEngine):
+class ViltAdapterEngine(SinglePassStep, ViltDatEngine):
     NPASS = 1
     ADAPTER_STEMS = ("adapter_",)
     COMM_ADAPTER = 0
@@ -30,7 +31,7 @@ class ViltAdapterEngine(ViltDatEngine):
             raise L.FeddatHipError("optimizer_mode adapter runs with 16-bit operands only (fp8=True is a dat configuration)")
         super().__init__(params, tasks, device, batch, res, fp8=False, **kw)
         self.opt_adapters = (0,)
-        self.loss_out = torch.zeros(4, device=self.dev)
+        self._init_single_pass()
 
     # ------------------------------------------------------------------------------------------ segment descriptors
     def _segs(self, layer: int, first: bool, bwd: bool):
@@ -62,47 +63,22 @@ class ViltAdapterEngine(ViltDatEngine):
             dict(x=self.top["h3"], dy=self.dcls, z=self.z, dz=self.dz, grad=self.ad[0].g[i * n:(i + 1) * n], rows=self.B,
                  scale=1.0)])
 
-    def _named_groups(self):
-        return [("adapter", self.ad[0]), ("head", self.head[self.task])]
+    # ------------------------------------------------------------------------------------------ train step (SinglePassStep)
+    def _trained(self):
+        return "adapter", self.ad[0]
 
-    # ------------------------------------------------------------------------------------------ train step
-    @_bound
-    def begin_local_update(self, task: str, steps_per_epoch: int, num_epochs: int = 15, warmup_ratio: float = 0.1,
-                           opt_adapters: Sequence[int] = (0,)):
-        """TaskTrainer.train prologue for optimizer_mode adapter (task_trainer.py:36-59): no teacher copy; a fresh AdamW over
-        adapter + head and a fresh poly schedule over steps_per_epoch * num_epochs ticks (one tick per batch)."""
-        self.task = task
-        self._start_local_update(steps_per_epoch, num_epochs, warmup_ratio, {})
-
-    @_bound
-    def _step_kernels(self):
-        B, task = self.B, self.task
-        hp = self.head[task]
+    def _step_refusal(self):
         if not self.fused_tail:
-            raise L.FeddatHipError("the single-adapter step runs on the fused step tail only")
-        self._forward_dual()                       # embed, layers at R rows, token-0 top layer, pooler (B rows)
-        logits = self._head_fwd(self.pooled[:B], "all", task)
-        flag = self.ovf_flags[0:1]
-        if self.n_valid < B:      # a short batch: the loss of the n valid rows, zero gradient in the replica rows
-            L.bce_loss_fwd_bwd_rows(logits, self.inp["target"], self.dlogits, self.loss_out, self.n_valid,
-                                    flag if self._dyn() else None)
-        else:
-            L.bce_loss_fwd_bwd(logits, self.inp["target"], self.dlogits, self.loss_out, flag if self._dyn() else None)
-        self._head_bwd(self.pooled[:B], "all", task, self.dpooled[:B])
-        self._backward_dual()                      # layers L-1 .. 1, layer-0 weight gradients, one reduce (+ inf check)
-        skip = dict(skip_if=(flag,)) if self._dyn() else {}
-        self._adamw_many([self._adamw_group(self.ad[0], **skip), self._adamw_group(hp, **skip)])
-        self.repack_adapter(0)
-        if self._dyn():
-            L.single_step_finish([self.ad[0].state, hp.state], flag, self.scaler_f, self.scaler_i, self.scale_growth,
-                                 self.scale_backoff, self.scale_growth_interval)
-        else:
-            L.step_tick_multi([self.ad[0].state, hp.state], [1, 1], [1, 1])
+            return "the single-adapter step runs on the fused step tail only"
 
-    def _loss_tensor(self):
-        """What train_step returns (task_trainer.py:433-450): the device tensor whose [0] is the reference's loss =
-        BCE_mean * num_labels."""
-        return self.loss_out
+    def _forward_train(self):
+        self._forward_dual()                       # embed, layers at R rows, token-0 top layer, pooler (B rows)
+
+    def _backward_train(self):
+        self._backward_dual()                      # layers L-1 .. 1, layer-0 weight gradients, one reduce (+ inf check)
+
+    def _after_adamw(self):
+        self.repack_adapter(0)
 
     # ------------------------------------------------------------------------------------------ inference / state
     def forward(self, batch: Dict[str, torch.Tensor], task: Optional[str] = None):

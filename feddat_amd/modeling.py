@@ -18,7 +18,7 @@ import torch
 
 from . import lib as L
 from .engine import ViltDatEngine, ENC
-from .modes import MODES, PROMPT_MODE, VECTOR_MODES, mode_names
+from .modes import ADAPTERLESS_MODES, MODES, PROMPT_MODE, SINGLE_PASS_MODES, VECTOR_MODES, mode_names
 
 
 class _Param:
@@ -218,21 +218,18 @@ class ViltContinualLearner:
         self.device = torch.device(device)
         self.optimizer_mode = optimizer_mode
         if optimizer_mode == "adapter":
-            from .adapter_engine import ViltAdapterEngine
-            Engine = ViltAdapterEngine
+            from .adapter_engine import ViltAdapterEngine as Engine
         elif optimizer_mode == "dat":
             Engine = ViltDatEngine
         elif optimizer_mode in VECTOR_MODES:
-            import functools
-            from .vector_engine import ViltVectorEngine
-            Engine = functools.partial(ViltVectorEngine, mode=optimizer_mode)
+            from .vector_engine import ViltVectorEngine as Engine
         elif optimizer_mode == PROMPT_MODE:
-            from .prompt_engine import ViltPromptEngine
-            Engine = ViltPromptEngine
+            from .prompt_engine import ViltPromptEngine as Engine
         else:
             raise L.FeddatHipError(f"optimizer_mode must be one of {MODES + (PROMPT_MODE,)}, got {optimizer_mode!r}")
         self.engine = Engine(params, self.ordered_cl_tasks, self.device, batch=batch_size, res=image_size, layers=num_layers,
                              lr=lr, operands=operands, num_labels=num_labels,
+                             **({"mode": optimizer_mode} if optimizer_mode in ADAPTERLESS_MODES else {}),
                              **({} if max_patches is None else {"max_patches": max_patches}))
         self.num_labels = int(num_labels)
         self.max_text_length = self.engine.Lt               # vilt.py:50: config.max_position_embeddings = 40
@@ -252,7 +249,7 @@ class ViltContinualLearner:
 
     # ---- adapter switches (vilt.py:363-373) ----
     def set_active_adapter(self, name):
-        if self.optimizer_mode in VECTOR_MODES + (PROMPT_MODE,):
+        if self.optimizer_mode in ADAPTERLESS_MODES:
             raise L.FeddatHipError(f"optimizer_mode {self.optimizer_mode} has no adapter (got {name!r})")
         if self.optimizer_mode == "adapter":
             if name != "adapter":
@@ -274,7 +271,7 @@ class ViltContinualLearner:
         """Which adapters a freshly created optimizer would hold (create_optimizer filters on requires_grad)."""
         if self.optimizer_mode == "adapter":
             return (0,)
-        if self.optimizer_mode in VECTOR_MODES + (PROMPT_MODE,):      # no adapter: the optimizer holds the mode's tensors and the head
+        if self.optimizer_mode in ADAPTERLESS_MODES:      # no adapter: the optimizer holds the mode's tensors and the head
             return ()
         return tuple(a for a in (0, 1) if self.adapter_requires_grad[a])
 
@@ -354,7 +351,7 @@ class ViltContinualLearner:
     def forward(self, task_key: str, images, texts=None):
         if not isinstance(images, dict):
             images = self.process_inputs(images, texts)
-        if self.optimizer_mode == "adapter" or self.optimizer_mode in VECTOR_MODES + (PROMPT_MODE,):
+        if self.optimizer_mode in SINGLE_PASS_MODES:
             return self.engine.forward(images, task_key)
         mode = "gating" if self.gating else self.active
         return self.engine.forward(images, mode, task_key)

@@ -46,6 +46,10 @@ MODES = ("dat", "adapter", "bias", "norm")
 VECTOR_MODES = ("bias", "norm")
 # prompt tuning (prompt_engine.ViltPromptEngine): known to mode_names / averaged_names and the Python surface, not to train.main
 PROMPT_MODE = "prompt"
+# the modes with no adapter in the backbone (single_pass.ViltFrozenEngine), and the modes that run the reference's non-dat
+# train_step, one pass per batch (single_pass.SinglePassStep): every mode but dat
+ADAPTERLESS_MODES = VECTOR_MODES + (PROMPT_MODE,)
+SINGLE_PASS_MODES = ("adapter",) + ADAPTERLESS_MODES
 
 
 def mode_names(keys: Sequence[str], mode: str) -> Dict[str, List[str]]:

@@ -26,7 +26,7 @@ from . import lib as L
 from . import vilt_spec
 from .fedavg import all_reduce_sum, allreduce_average, get_average_net  # noqa: F401  (re-exported: main.py:50)
 from .modeling import ViltContinualLearner, convert_batch_to_vilt_input_dict, create_vilt_continual_learner_model
-from .modes import MODES, PROMPT_MODE, VECTOR_MODES, mode_names
+from .modes import ADAPTERLESS_MODES, MODES, SINGLE_PASS_MODES, mode_names
 
 
 class OptimizerHandle:
@@ -162,7 +162,7 @@ class TaskTrainer:
         optimizer_mode adapter: one forward / backward / AdamW step / scheduler tick (task_trainer.py:433-450); returns
         loss = BCE * num_labels.  optimizer_mode bias / norm / prompt: the same step on the adapter-less model."""
         out = model.engine.train_step(self.encode_batch(model, batch), use_graph=self.use_graph)
-        if self._mode(model) == "adapter" or self._mode(model) in VECTOR_MODES + (PROMPT_MODE,):
+        if self._mode(model) in SINGLE_PASS_MODES:
             return out[0]
         model.activate_gating()
         model.set_active_adapter("adapter_0")
@@ -183,7 +183,7 @@ class TaskTrainer:
 
     def eval(self, model: ViltContinualLearner):
         loader = self.vqa_test_dataloader
-        if self._mode(model) in VECTOR_MODES + (PROMPT_MODE,):      # no adapter to switch: one score
+        if self._mode(model) in ADAPTERLESS_MODES:      # no adapter to switch: one score
             return self.eval_one_loader(model, loader)
         if self._mode(model) == "adapter":      # task_trainer.py:232-233,246: one score
             model.set_active_adapter("adapter")

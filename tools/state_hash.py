@@ -4,13 +4,14 @@ settings: every group the step updates (_named_groups(), in that order: adapter_
 with the same hash run the same arithmetic: at 80 steps the AdamW trajectory is chaotic enough that a last-bit change moves the
 round-length parity draws ("draws"), so a change meant to be arithmetic-neutral -- a kernel, or the host
 sequencing of an engine -- is checked with this before the 80-step tests are trusted.
-python tools/state_hash.py [repo root] [--engine dat | dat-fp8 | adapter | bias | norm | albef]
+python tools/state_hash.py [repo root] [--engine dat | dat-fp8 | adapter | bias | norm | prompt | albef] [--layers N]
 (albef: the full-size AlbefDatEngine at B = 4, default settings -- the LM head frozen --, 12 replayed steps; the repo root is the tree whose feddat_amd is hashed, so one copy of this tool compares two trees)
-dat, round 6 HEAD (= round 5's arithmetic): cb900273526616cd; the other engines: DESIGN.md sections 13 and 14"""
+dat, round 6 HEAD (= round 5's arithmetic): cb900273526616cd; the other engines: DESIGN.md sections 13, 14 and 21 (prompt, and --layers 1)"""
 import argparse, sys, os, hashlib, torch
 ap = argparse.ArgumentParser()
 ap.add_argument("root", nargs="?", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-ap.add_argument("--engine", choices=("dat", "dat-fp8", "adapter", "bias", "norm", "albef"), default="dat")
+ap.add_argument("--engine", choices=("dat", "dat-fp8", "adapter", "bias", "norm", "prompt", "albef"), default="dat")
+ap.add_argument("--layers", type=int, default=12, help="encoder layers of the ViLT engines (1: the top layer is layer 0)")
 args = ap.parse_args()
 root = args.root
 sys.path.insert(0, root)
@@ -30,15 +31,18 @@ if args.engine == "albef":
     print(os.path.basename(root), args.engine, h.hexdigest()[:16], float(e.comm_flat().double().abs().sum()), float(e._loss_tensor()[0]))
     sys.exit(0)
 mode = "dat" if args.engine.startswith("dat") else args.engine
-params = vilt_spec.random_init(12, ["c0"], seed=0, optimizer_mode=mode)
+params = vilt_spec.random_init(args.layers, ["c0"], seed=0, optimizer_mode=mode)
 batches = [vilt_spec.synthetic_batch(32, 384, 1234 + i, device=dev) for i in range(4)]
-size = dict(batch=32, res=384, layers=12)
+size = dict(batch=32, res=384, layers=args.layers)
 if mode == "dat":
     e = engine.ViltDatEngine(params, ["c0"], dev, fp8=args.engine == "dat-fp8", **size)
     e.top_q_cls = False
 elif mode == "adapter":
     from feddat_amd.adapter_engine import ViltAdapterEngine
     e = ViltAdapterEngine(params, ["c0"], dev, **size)
+elif mode == "prompt":
+    from feddat_amd.prompt_engine import ViltPromptEngine
+    e = ViltPromptEngine(params, ["c0"], dev, **size)
 else:
     from feddat_amd.vector_engine import ViltVectorEngine
     e = ViltVectorEngine(params, ["c0"], dev, mode=mode, **size)
