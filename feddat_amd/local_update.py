@@ -1,5 +1,5 @@
 """Host-side protocol that every local-update engine shares around its HIP step (the ViLT engines on vilt_backbone.ViltBackbone --
-ViltDatEngine, ViltAdapterEngine, ViltVectorEngine -- and AlbefDatEngine): the flat trainable groups, the device-side loss scaler
+ViltDatEngine, ViltAdapterEngine, ViltVectorEngine -- and albef_engine.AlbefDatEngine on albef_backbone.AlbefBackbone): the flat trainable groups, the device-side loss scaler
 (GradScaler on the device), the AdamW launches and the DAT optimizer tail, the start of a local update,
 hipGraph capture, and the trainable state.
 

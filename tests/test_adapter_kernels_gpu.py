@@ -117,7 +117,7 @@ def _cases():
         c.append((f"vilt_top_B{B}", 2 * B, _vilt(B)))
     for rows in (185 * 32, 32):      # ViltAdapterEngine._segs / _top_segs (adapter_engine.py): one segment, one adapter
         c.append((f"adapter_mode_{rows}", rows, [_seg(0, rows, ((0, 1.0),))]))
-    for rows in (32 * 577, 32 * 25, 32 * 25 + 1):     # AlbefEngine._segs (albef_engine.py): image rows, question rows, odd
+    for rows in (32 * 577, 32 * 25, 32 * 25 + 1):     # AlbefBackbone._segs (albef_backbone.py): image rows, question rows, odd
         h = rows // 2
         c.append((f"albef_both_{rows}", rows, [_seg(0, h, GATED), _seg(h, rows, AD1)]))
         c.append((f"albef_gating_{rows}", rows, [_seg(0, rows, GATED)]))
