@@ -3,6 +3,11 @@
 The HIP library is THE product path: if it cannot be loaded this module raises -- there is no eager /
 PyTorch / CPU fallback anywhere in feddat_amd.  torch is used only as plumbing: device allocations
 (tensor.data_ptr()), the current HIP stream, and torch.distributed for the one RCCL all-reduce per round.
+
+The headers are the one statement of the C ABI: every entry point's argument and return types and the fields of the ten
+structs are read from them at import (feddat_amd/cheader.py), nothing of that is restated here.  A new entry point is declared
+in its header and gets its wrapper below.  The numeric constants are literals here (tests/test_binding_cpu.py holds them to
+the headers' #defines).
 """
 from __future__ import annotations
 
@@ -13,6 +18,8 @@ import threading
 from typing import Optional, Sequence
 
 import torch  # imported first on purpose: libfeddat_hip.so must bind to the HIP runtime torch already loaded
+
+from . import cheader as _H
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_PKG, "libfeddat_hip.so")
@@ -31,61 +38,19 @@ FILTER_BILINEAR, FILTER_BICUBIC = 2, 3      # FEDDAT_FILTER_*: Pillow's Image.BI
 ABI_VERSION = 8
 vp, i32, i64, f32, u32 = C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_uint
 
-
-class AdapterSeg(C.Structure):
-    _fields_ = [("row_begin", i32), ("row_end", i32), ("n_adapters", i32), ("train_slot", i32),
-                ("x_row_delta", i32), ("reserved", i32), ("scale", f32 * 2), ("wd", vp * 2), ("wdT", vp * 2), ("wu", vp * 2), ("wuT", vp * 2),
-                ("bd", vp * 2), ("bu", vp * 2)]
-
-
-class WgradSeg(C.Structure):
-    _fields_ = [("x", vp), ("dy", vp), ("z", vp), ("dz", vp), ("grad", vp), ("rows", i32), ("scale", f32),
-                ("grad_unscale", f32), ("reserved", i32), ("grad_unscale_dev", vp)]
-
-
-class ViltLayerWeights(C.Structure):
-    _fields_ = [(n, vp) for n in ("wqkv", "wo", "w1", "w2", "wqkvT", "woT", "w1T", "w2T", "bqkv", "bo", "b1", "b2", "ln1_g",
-                                  "ln1_b", "ln2_g", "ln2_b")] + [("ln_eps", f32)]
-
-
-class ViltLayerActs(C.Structure):
-    _fields_ = [(n, vp) for n in ("h_in", "st1", "qkv", "ctx", "lse", "h2", "st2", "u", "h3", "z_save", "h_out", "x16", "f16",
-                                  "st1_next")]
-
-
-class ViltLayerGrads(C.Structure):
-    _fields_ = [(n, vp) for n in ("dh_out", "dh_in", "dh3", "dh16", "dU", "dx16", "dctx", "dqkv", "z", "dz")]
-
-
-class VgradJob(C.Structure):         # feddat_vgrad_job
-    _fields_ = [("partials", vp), ("grad", vp), ("slabs", i32), ("n", i32), ("flags", i32), ("reserved", i32)]
-
+# the structs of include/feddat_hip.h: their _fields_ are the header's, read by cheader
+AdapterSeg = _H.MAIN.types["feddat_adapter_seg"]
+WgradSeg = _H.MAIN.types["feddat_wgrad_seg"]
+ViltLayerWeights = _H.MAIN.types["feddat_vilt_layer_weights"]
+ViltLayerActs = _H.MAIN.types["feddat_vilt_layer_acts"]
+ViltLayerGrads = _H.MAIN.types["feddat_vilt_layer_grads"]
+VgradJob = _H.MAIN.types["feddat_vgrad_job"]
+HtJob = _H.MAIN.types["feddat_ht_job"]
+AdamwGroup = _H.MAIN.types["feddat_adamw_group"]
+GemmRoute = _H.MAIN.types["feddat_gemm_route_t"]
+HtPlan = _H.MAIN.types["feddat_ht_plan"]
 
 VGRAD_UNSCALED = 1
-
-
-class HtJob(C.Structure):            # feddat_ht_job
-    _fields_ = [("A", vp), ("sa_i", i64), ("sa_k", i64), ("B", vp), ("sb_k", i64), ("sb_j", i64), ("I", i32), ("J", i32),
-                ("K", i32), ("mode", i32), ("alpha", f32), ("bias_j", vp), ("out", vp), ("ldo", i64), ("colsum", vp),
-                ("pro", i32), ("pro_a", vp), ("pro_b", vp), ("pro_eps", f32), ("stats_out", vp), ("epi", i32), ("aux", vp),
-                ("ld_aux", i64), ("alpha_dev", vp)]
-
-
-class AdamwGroup(C.Structure):       # feddat_adamw_group
-    _fields_ = [("p", vp), ("g", vp), ("m", vp), ("v", vp), ("n", i64), ("seg_off", vp), ("seg_wd", vp), ("nseg", i32),
-                ("state", vp), ("d_sched", i32), ("d_adam", i32), ("skip_if", vp * 2), ("bak", vp), ("bak_mode", i32),
-                ("restore_if", vp)]
-
-
-class GemmRoute(C.Structure):       # feddat_gemm_route_t
-    _fields_ = [(n, C.c_int) for n in ("family", "rows", "threads", "lds_bytes", "grid", "bm", "tiles_m", "nx", "tm_per", "tn_per",
-                                       "dbg")]
-
-
-class HtPlan(C.Structure):          # feddat_ht_plan
-    _fields_ = [(n, C.c_int) for n in ("avec", "bvec", "jt", "itiles", "jblocks", "blocks")]
-
-
 HT_PRO_NONE, HT_PRO_LN, HT_PRO_TANH_BWD = 0, 1, 2
 HT_EPI_NONE, HT_EPI_TANH, HT_EPI_MUL_DGELU = 0, 1, 2
 
@@ -99,138 +64,12 @@ def _fill(struct, **tensors):
     return s
 
 
-_SIGS = {
-    "feddat_abi_version": [],
-    "feddat_operand_format": [],
-    "feddat_ctx_create": [i32, C.POINTER(vp)],
-    "feddat_ctx_destroy": [vp],
-    "feddat_ctx_device": [vp, C.POINTER(i32), C.POINTER(i32)],
-    "feddat_set_debug_flags": [i32],
-    "feddat_comm_unique_id": [vp],
-    "feddat_comm_create": [vp, i32, i32, C.POINTER(vp)],
-    "feddat_comm_create_timeout": [vp, i32, i32, i32, C.POINTER(vp)],
-    "feddat_comm_destroy": [vp],
-    "feddat_fedavg_allreduce": [vp, vp, vp, i64, f32, f32, vp],
-    "feddat_comm_info": [vp, vp, vp, vp],
-    "feddat_gemm_bf16_nt": [vp, i32, vp, i32, i32, i32, i32, i32, vp, vp, i32, vp, i32, vp, i32, vp, i32, vp, i32, vp],
-    "feddat_gemm_skinny_workspace_elems": [i32, i32, i32],
-    "feddat_gemm_dual_blocks_per_cu": [vp],
-    "feddat_gemm_route": [i32, i32, i32, i32, i32, i32, i32, C.POINTER(GemmRoute)],
-    "feddat_gemm_fp8_nt": [vp, i32, vp, vp, i32, vp, i32, i32, i32, i32, vp, vp, i32, vp, i32, vp, i32, vp],
-    "feddat_layernorm_bwd_dx_fp8": [vp, vp, i64, vp, i64, vp, vp, vp, i64, i32, i32, vp, i64, vp, vp, vp],
-    "feddat_gemm_fp8mx_nt": [vp, i32, vp, i32, vp, i32, vp, i32, i32, i32, vp, vp, i32, vp],
-    "feddat_gemm_fp8_nt_f32": [vp, i32, vp, vp, i32, vp, i32, i32, i32, vp, vp, i32, vp, i32, vp],
-    "feddat_quant_rows_fp8": [vp, i64, i32, i32, vp, vp, vp],
-    "feddat_layernorm_fwd_fp8": [vp, i64, vp, vp, f32, i32, i32, vp, vp, vp, vp, vp],
-    "feddat_gemm_bf16_nt_skinny": [vp, i32, vp, i32, i32, i32, i32, i32, vp, vp, i32, vp, i32, vp, i32, vp, i32, vp, i32,
-                                   vp, i64, vp],
-    "feddat_attn_fwd": [vp, vp, vp, vp, i32, i32, i32, vp],
-    "feddat_attn_bwd": [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp],
-    "feddat_attn_bwd_fp8mx": [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp],
-    "feddat_attn_cls_fwd": [vp, vp, vp, vp, i32, i32, i32, vp],
-    "feddat_attn_cls_bwd": [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp],
-    "feddat_attn2_fwd": [vp, i64, vp, i64, vp, i64, vp, i32, vp, i64, vp, i32, i32, i32, i64, i64, i32, vp],
-    "feddat_attn2_bwd": [vp, i64, vp, i64, vp, i64, vp, i32, vp, i64, vp, vp, i64, vp, vp, i64, vp, i64, vp, i64, i32, i32,
-                         i32, i64, i64, i32, vp],
-    "feddat_attn2_fwd_dropout": [vp, i64, vp, i64, vp, i64, vp, i32, vp, i64, vp, i32, i32, i32, i64, i64, i32, f32, u32, u32,
-                                 vp, vp],
-    "feddat_attn2_bwd_dropout": [vp, i64, vp, i64, vp, i64, vp, i32, vp, i64, vp, vp, i64, vp, vp, i64, vp, i64, vp, i64,
-                                 i32, i32, i32, i64, i64, i32, f32, u32, u32, vp, vp],
-    "feddat_dropout": [vp, vp, vp, vp, vp, i64, f32, u32, u32, vp, vp],
-    "feddat_layernorm_fwd": [vp, i64, vp, vp, f32, i32, i32, vp, vp, vp, vp],
-    "feddat_layernorm_bwd_dx": [vp, vp, i64, vp, i64, vp, vp, vp, i64, i32, i32, vp, i64, vp, vp],
-    "feddat_layernorm_bwd_dx_sparse": [vp, vp, i64, vp, i64, vp, vp, vp, i64, i32, i32, i32, vp, i64, vp, vp],
-    "feddat_layernorm_bwd_full": [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp],
-    "feddat_adapter_fwd": [vp, vp, i32, i32, i32, C.POINTER(AdapterSeg), i32, vp, vp],
-    "feddat_adapter_fwd_ln": [vp, vp, i32, i32, i32, C.POINTER(AdapterSeg), i32, vp, vp, f32, vp, vp, vp, vp],
-    "feddat_adapter_bwd": [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, C.POINTER(AdapterSeg), i32, vp],
-    "feddat_adapter_bwd_fp8": [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, C.POINTER(AdapterSeg), i32, vp],
-    "feddat_adapter_pack": [vp, vp, vp, vp, vp, vp, i32, i32, vp],
-    "feddat_adapter_pack_strided": [vp, vp, i64, vp, vp, vp, vp, i64, i32, i32, i32, vp],
-    "feddat_adapter_wgrad_workspace_elems": [i32],
-    "feddat_adapter_wgrad": [C.POINTER(WgradSeg), i32, vp, i64, i32, i32, vp],
-    "feddat_adapter_wgrad_partial": [C.POINTER(WgradSeg), i32, vp, i64, i32, i32, vp],
-    "feddat_adapter_wgrad_reduce": [vp, i32, i32, vp, i64, vp],
-    "feddat_adapter_wgrad_reduce_checked": [vp, i32, i32, vp, i64, vp, vp],
-    "feddat_vilt_layer_fwd": [vp, C.POINTER(ViltLayerWeights), C.POINTER(ViltLayerActs), i32, i32, i32, vp, i32,
-                              C.POINTER(AdapterSeg), i32, vp, vp, vp],
-    "feddat_vilt_layer_bwd": [vp, C.POINTER(ViltLayerWeights), C.POINTER(ViltLayerActs), C.POINTER(ViltLayerGrads), i32, i32,
-                              i32, vp, C.POINTER(AdapterSeg), i32, C.POINTER(WgradSeg), i32, vp, i64, i32, vp],
-    "feddat_sgemm_f32": [vp, i64, i64, vp, i64, i64, i32, i32, i32, i32, f32, vp, vp, i64, i64, vp, i64, vp],
-    "feddat_reduce_partials": [vp, i64, i32, i64, vp, vp],
-    "feddat_dat_loss_fwd_bwd": [vp, vp, vp, i32, i32, f32, vp, vp, vp],
-    "feddat_dat_loss_fwd_bwd_single": [vp, vp, vp, i32, i32, f32, vp, vp, vp],
-    "feddat_dat_loss_fwd_bwd_checked": [vp, vp, vp, i32, i32, f32, vp, vp, vp, vp],
-    "feddat_dat_step_finish": [vp, vp, vp, vp, vp, vp, f32, f32, i32, vp],
-    "feddat_bce_loss_fwd_bwd": [vp, vp, i32, i32, vp, vp, vp, vp],
-    "feddat_single_step_finish": [C.POINTER(vp), i32, vp, vp, vp, f32, f32, i32, vp],
-    "feddat_dat_loss_fwd_bwd_rows": [vp, vp, vp, i32, i32, i32, f32, vp, vp, vp, vp],
-    "feddat_bce_loss_fwd_bwd_rows": [vp, vp, i32, i32, i32, vp, vp, vp, vp],
-    "feddat_dat_loss_wide_workspace_elems": [i32],
-    "feddat_dat_loss_fwd_bwd_wide": [vp, vp, vp, i32, i32, i32, f32, vp, vp, vp, vp, i64, vp],
-    "feddat_vector_grad_workspace_elems": [i32, i32],
-    "feddat_colsum_partial": [vp, vp, i64, vp, i32, i32, vp, i64, vp],
-    "feddat_ln_param_grad_partial": [vp, vp, i64, vp, i64, vp, i32, i32, vp, vp, i64, vp],
-    "feddat_vector_grad_reduce": [vp, i32, i32, f32, vp, vp, vp],
-    "feddat_head_gemm": [C.POINTER(HtJob), i32, vp],
-    "feddat_head_gemm_plan": [C.POINTER(HtJob), C.POINTER(HtPlan)],
-    "feddat_head_ln_gelu": [vp, vp, vp, f32, i32, i32, vp, vp, vp, vp],
-    "feddat_head_ln_bwd_full": [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp],
-    "feddat_adamw_multi": [C.POINTER(AdamwGroup), i32, f32, i32, i32, f32, f32, f32, vp],
-    "feddat_step_tick_multi": [C.POINTER(vp), C.POINTER(i32), C.POINTER(i32), i32, vp],
-    "feddat_vqa_score_accumulate": [vp, vp, i32, i32, vp, vp],
-    "feddat_lm_loss_fwd_bwd": [vp, vp, i64, vp, vp, vp, i32, i32, f32, f32, f32, vp, i64, vp, vp],
-    "feddat_lm_loss_fwd_bwd_dyn": [vp, vp, i64, vp, vp, vp, i32, i32, f32, f32, f32, vp, vp, vp, i64, vp, vp],
-    "feddat_axpby3": [vp, f32, vp, f32, vp, f32, vp, vp, i64, vp],
-    "feddat_vilt_stage_inputs": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],
-    "feddat_vilt_pad_batch": [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],
-    "feddat_softmax_gather_rows": [vp, i64, i32, i32, vp, i64, i32, vp, vp],
-    "feddat_topk_rows": [vp, i64, vp, i32, i32, i32, i32, vp, vp, vp],
-    "feddat_albef_pad_questions": [vp, vp, vp, i32, i32, i64, i32, vp],
-    "feddat_rank_slab_gather": [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i64, vp],
-    "feddat_rank_slab_loss": [vp, vp, i32, i32, i32, i32, i32, i32, vp],
-    "feddat_lm_head_refresh": [vp, vp, i32, i32, i32, vp, vp, vp, vp],
-    "feddat_gather_rows": [vp, vp, vp, vp, i32, i32, vp],
-    "feddat_segment_sum_rows": [vp, vp, vp, i32, i32, i32, vp],
-    "feddat_adamw_flat": [vp, vp, vp, vp, i64, vp, vp, i32, vp, f32, i32, i32, f32, f32, f32, vp],
-    "feddat_step_tick": [vp, i32, i32, vp],
-    "feddat_text_embed": [vp, vp, vp, vp, vp, vp, vp, f32, vp, vp, i32, i32, i32, i32, vp],
-    "feddat_im2col_patches": [vp, vp, i32, i32, i32, i32, i32, vp],
-    "feddat_image_embed_assemble": [vp, vp, vp, vp, i64, vp, vp, i32, i32, i32, i32, i32, vp],
-    "feddat_image_embed_assemble_masked": [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp],
-    "feddat_im2col_patches_slots": [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp],
-    "feddat_image_embed_assemble_slots": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp],
-    "feddat_pos_embed_resize_masked": [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],
-    "feddat_vilt_key_mask": [vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],
-    "feddat_vilt_image_workspace_bytes": [vp, vp, vp, vp, i32],
-    "feddat_vilt_image_preprocess": [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, i64, vp],
-    "feddat_image_resample_workspace_bytes": [vp, vp, vp, vp, i32, i32],
-    "feddat_image_resample_u8": [vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, i64, vp],
-    "feddat_albef_image_workspace_bytes": [vp, vp, i32, i32],
-    "feddat_albef_image_preprocess": [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, i64, vp],
-    "feddat_pos_embed_resize": [vp, vp, i32, i32, i32, i32, vp],
-    "feddat_wordpiece_table_entries": [i32],
-    "feddat_wordpiece_table_build": [vp, vp, i32, vp, i64],
-    "feddat_wordpiece_encode": [vp, vp, i32, vp, i64, i32, i32, i32, i32, i32, vp, vp, vp, vp],
-    "feddat_cvt_f32_bf16": [vp, vp, i64, vp],
-    "feddat_transpose_f32_bf16": [vp, vp, i32, i32, vp],
-    "feddat_tanh_fwd": [vp, i64, vp],
-    "feddat_tanh_bwd": [vp, vp, vp, i64, vp],
-    "feddat_gelu_fwd": [vp, vp, i64, vp],
-    "feddat_gelu_bwd": [vp, vp, vp, i64, vp],
-    "feddat_scatter_cls_rows": [vp, vp, vp, i32, i32, i32, vp],
-    "feddat_fedavg_accumulate": [vp, vp, i64, f32, f32, i32, vp],
-    "feddat_probe_tr16": [vp, vp, vp],
-}
-
-EXPORTED_SYMBOLS = tuple(_SIGS.keys())
-
-# the extension header include/feddat_hip_prompt.h (csrc/prompt.hip): the same libraries, their own table
-_PROMPT_SIGS = {
-    "feddat_prompt_frame_assemble": [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp],
-    "feddat_prompt_grad_gather": [vp, i32, i32, i32, i32, f32, vp, vp, vp, vp],
-}
-PROMPT_SYMBOLS = tuple(_PROMPT_SIGS.keys())
+# every entry point's argument types as its header declares them (cheader's type rules), in declaration order
+_SIGS = {name: [t for t, _ in params] for name, (_, params) in _H.MAIN.functions.items()}
+EXPORTED_SYMBOLS = tuple(_SIGS)
+# the extension header include/feddat_hip_prompt.h (csrc/prompt.hip): the same libraries
+_PROMPT_SIGS = {name: [t for t, _ in params] for name, (_, params) in _H.PROMPT.functions.items()}
+PROMPT_SYMBOLS = tuple(_PROMPT_SIGS)
 
 
 class FeddatHipError(RuntimeError):
@@ -248,10 +87,10 @@ def _open(path: str, want_format: int) -> C.CDLL:
             f"{path} not found: the HIP library is the only implementation of this path "
             "(no CPU/PyTorch fallback). Build it with `python __graft_entry__.py` or `python -m feddat_amd.build`.")
     lib = C.CDLL(path)
-    for name, args in list(_SIGS.items()) + list(_PROMPT_SIGS.items()):
-        fn = getattr(lib, name)
-        fn.argtypes = args
-        fn.restype = i64 if name.endswith(("_workspace_elems", "_workspace_bytes", "_table_entries")) else i32
+    for header, sigs in ((_H.MAIN, _SIGS), (_H.PROMPT, _PROMPT_SIGS)):
+        for name, args in sigs.items():
+            fn = getattr(lib, name)
+            fn.argtypes, fn.restype = args, header.functions[name][0]
     if lib.feddat_abi_version() != ABI_VERSION:
         raise FeddatHipError(f"{os.path.basename(path)} ABI version mismatch")
     if lib.feddat_operand_format() != want_format:
