@@ -60,7 +60,16 @@ def lm_head_group_spec(vocab: int, H: int = 768):
 class AlbefBackbone(LocalUpdateEngine):
     """The frozen ALBEF model with its adapters, buffers and forward.  A class on top sets the operand format
     (_init_loss_scale) and train_lm_head, then calls _init_backbone (the model) and _alloc (the buffers) inside
-    `with lib.operands(...)`."""
+    `with lib.operands(...)`.
+
+    ADAPTER_STEMS names the adapters every module carries, one flat group and one 16-bit pack each (slot a = stem a): the three of
+    DAT here, ("adapter_",) in the single-adapter FedAvg engine (albef_adapter_engine.AlbefAdapterEngine).  What else depends on
+    the adapter set follows from it: FROZEN_ADAPTERS (slots without optimizer state: DAT's teacher), ACT_SETS (the activation
+    sets _alloc makes, named after the adapter modes whose forward they keep; a forward in any other mode borrows the last:
+    albef_rank._as_mode) and the mode -> segment table (_mode_segments)."""
+    ADAPTER_STEMS = ("adapter_0_", "adapter_1_", "adapter_2_")
+    FROZEN_ADAPTERS = (2,)
+    ACT_SETS = ("gating", "adapter_1")
 
     def _init_backbone(self, params, device, batch, n_answers, q_len, a_len, vit_depth, enc_layers, fusion_layer, dec_layers, image,
                        vocab, lr, weight_decay, adam_eps, pad_id, max_pos, dropout, seed, stack_text):
@@ -188,15 +197,15 @@ class AlbefBackbone(LocalUpdateEngine):
             [f"text_encoder.encoder.layer.{i}.output.adapter." for i in range(enc_layers)] + \
             [f"text_decoder.bert.encoder.layer.{i}.output.adapter." for i in range(dec_layers)]
         shp = {"down.weight": (self.r, H), "down.bias": (self.r,), "up.weight": (H, self.r), "up.bias": (H,)}
-        self.ad = [FlatGroup([(PRE + m + f"adapter_{a}_{t}", shp[t]) for m in self.modules for t in ADAPTER_TENSORS], dev,
-                             with_opt=(a != 2)) for a in range(3)]
+        self.ad = [FlatGroup([(PRE + m + stem + t, shp[t]) for m in self.modules for t in ADAPTER_TENSORS], dev,
+                             with_opt=(a not in self.FROZEN_ADAPTERS)) for a, stem in enumerate(self.ADAPTER_STEMS)]
         for grp in self.ad:
             for n in grp.names:
                 grp.view(n).copy_(params[n].to(dev, torch.float32))
         self.ad_numel = self.r * H + self.r + H * self.r + H
         nm = len(self.modules)
-        self._pack16 = [torch.empty(nm, 4, self.r * H, dtype=self.op_dtype, device=dev) for _ in range(3)]
-        for a in range(3):
+        self._pack16 = [torch.empty(nm, 4, self.r * H, dtype=self.op_dtype, device=dev) for _ in self.ad]
+        for a in range(len(self.ad)):
             self.repack_adapter(a)
         self._segs_cache: Dict = {}
         # stack_text (round 4, OFF by default -- measured slower): with dropout = 0 the text towers of the gated and the
@@ -287,7 +296,9 @@ class AlbefBackbone(LocalUpdateEngine):
 
         def act_set():
             return dict(vit=vit_set(), **text_set(1), loss=f32(4 + 2 * self.R))
-        self.acts = {"gating": act_set(), "adapter_1": act_set()}
+        self.acts = {m: act_set() for m in self.ACT_SETS}
+        if len(self.ACT_SETS) == 1:      # one pass per step: nothing to share between passes, nothing to stack
+            return
         # Everything in the image encoder AHEAD of block 0's adapter (patch embedding, block 0's attention and MLP) is frozen
         # and sees the same image in both passes: train_step computes it once (_vit_fwd(..., part="prefix")), both activation
         # sets point at the same buffers (read-only in the backward: block 0's adapter input h3 for its weight gradient).
@@ -308,7 +319,7 @@ class AlbefBackbone(LocalUpdateEngine):
     def _pack(self, a: int, m: int):
         c = self._pack16[a][m]
         H, r = self.H, self.r
-        base = PRE + self.modules[m] + f"adapter_{a}_"
+        base = PRE + self.modules[m] + self.ADAPTER_STEMS[a]
         return dict(wd=c[0].view(r, H), wdT=c[1].view(H, r), wu=c[2].view(H, r), wuT=c[3].view(r, H),
                     bd=self.ad[a].view(base + "down.bias"), bu=self.ad[a].view(base + "up.bias"),
                     wd32=self.ad[a].view(base + "down.weight"), wu32=self.ad[a].view(base + "up.weight"))
@@ -326,11 +337,16 @@ class AlbefBackbone(LocalUpdateEngine):
         g, hd = self.lm, self.head
         L.lm_head_refresh(g.view(g.names[0]), g.view(g.names[4]), hd["t"]["w"], hd["t"]["wT"], hd["b"])
 
-    @staticmethod
-    def _mode_segments(mode: str, rows: int):
+    @classmethod
+    def _mode_segments(cls, mode: str, rows: int):
         """The row segments of a pass over `rows` rows as [(row_begin, row_end, [(adapter, scale), ...])]; the FIRST adapter of
         a segment is the one that pass trains.  A single pass is one segment -- "gating": adapter_0 and the teacher adapter_2 at
-        0.5 each, "adapter_k": adapter k alone; "both" is two: rows [0, rows / 2) gated, [rows / 2, rows) adapter_1."""
+        0.5 each, "adapter_k": adapter k alone; "both" is two: rows [0, rows / 2) gated, [rows / 2, rows) adapter_1.  With one
+        adapter per module (ADAPTER_STEMS of one) the only mode is "adapter": that adapter alone at scale 1."""
+        if len(cls.ADAPTER_STEMS) == 1:
+            if mode != "adapter":
+                raise L.FeddatHipError(f"a single-adapter model runs in mode 'adapter' only, got {mode!r}")
+            return [(0, rows, [(0, 1.0)])]
         gated, h = [(0, 0.5), (2, 0.5)], rows // 2
         if mode == "both":
             return [(0, h, gated), (h, rows, [(1, 1.0)])]

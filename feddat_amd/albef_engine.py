@@ -62,11 +62,11 @@ class AlbefDatEngine(AlbefRank, AlbefBackbone):
         """Weight-gradient partial sums: one slot per adapter module and pass; ONE batched reduction per backward pass folds them
         into the flat gradient buffers (feddat_adapter_wgrad_partial / _reduce) instead of one reduce launch per module.  A slot
         holds the partial sums of the pass's segments: one, or two for the stacked pair."""
-        modes = ("gating", "adapter_1") + (("both",) if self.batch_text else ())
+        modes = self.ACT_SETS + (("both",) if self.batch_text else ())
         ws = {n: L.adapter_wgrad_workspace_elems(n) for n in ((1, 2) if self.batch_text else (1,))}
         self.wpart_stride = {m: ws[2 if m == "both" else 1] for m in modes}
         self.wpart = {m: torch.empty(len(self.modules) * self.wpart_stride[m], device=self.dev) for m in modes}
-        self._wg_done = {m: [] for m in ("gating", "adapter_1", "both")}
+        self._wg_done = {m: [] for m in self.ACT_SETS + ("both",)}
 
     def _alloc_step(self):
         """What the backward and the step need besides: the schedule's host state, the loss scaler, one scratch set per pass
@@ -75,7 +75,7 @@ class AlbefDatEngine(AlbefRank, AlbefBackbone):
         f32, b16 = self._f32, self._b16
         B, N, Lq, La = self.B, self.N, self.Lq, self.La
         self.sched = dict(warmup=1, total=2)
-        self.opt_adapters = (0, 1)
+        self.opt_adapters = tuple(a for a in range(len(self.ad)) if a not in self.FROZEN_ADAPTERS)
         self.graph = None
         self.side = None           # second stream of train_step (created lazily on the engine's device)
         self._alloc_scaler()
@@ -92,7 +92,7 @@ class AlbefDatEngine(AlbefRank, AlbefBackbone):
                         z=f32(M, self.r), dz=f32(M, self.r), dsum=f32(k * max(B, N), self.heads, max(self.Ni, Lq, La)),
                         d_img=f32(k * self.Mi, H), d_qs=f32(k * self.Mq, H), d_rep=f32(k * N * Lq, H), d_dec=f32(k * self.Ma, H))
         self.gs = {m: scratch(2 if m == "both" else 1) for m in self.wpart}
-        if self.dropout > 0:       # teacher logits of P0: the gated text pass is re-run (other masks) for P2
+        if self.dropout > 0 and len(self.ACT_SETS) > 1:       # teacher logits of P0: the gated text pass is re-run (other masks) for P2
             self.logits_all = torch.empty(self.R, self.Vp, device=dev)
         if self.train_lm_head:
             self._alloc_head_grads()
@@ -141,7 +141,7 @@ class AlbefDatEngine(AlbefRank, AlbefBackbone):
         leaves through LocalUpdateEngine._scale_out."""
         if not self._dyn():
             return dict(grad_scale=self.loss_scale)
-        a = 0 if mode == "gating" else 1
+        a = self._mode_segments(mode, 2)[0][2][0][0]      # the adapter the pass trains: its flag ("gating": 0, "adapter_1": 1)
         return dict(grad_scale=1.0, grad_scale_dev=self.scaler_f[0:1], nonfinite=self.ovf_flags[a:a + 1])
 
     # ------------------------------------------------------------------------------------------ trainable LM head

@@ -2,6 +2,8 @@
 
     model = create_albef_continual_learner_model(params, device, batch_size, n_answers, ...)
     model.activate_gating(); model.set_active_adapter('adapter_0')      # albef.py:139-171 fan-out over the 30 Adapter modules
+                                                 # optimizer_mode="adapter" (the single-adapter FedAvg baseline, main.py:114-118,
+                                                 # 141-149): set_active_adapter('adapter') is the only switch the model has
     loss, logits = model(task_key, batch)        # batch['train'] = True : ALBEF.forward(train=True)  (albef.py:52-60)
     ids, probs   = model(task_key, batch)        # batch['train'] = False: rank_answer over batch['answer_list'] (albef.py:61-73)
                                                  # any nq <= batch_size questions (a short last batch), any k <= len(answer_list),
@@ -23,6 +25,7 @@ from typing import Dict, List, Sequence
 import torch
 
 from . import lib as L
+from .albef_adapter_engine import AlbefAdapterEngine
 from .albef_engine import AlbefDatEngine
 
 
@@ -31,8 +34,12 @@ class ALBEFContinualLearner:
 
     def __init__(self, params: Dict[str, torch.Tensor], device, batch_size: int, n_answers: int, q_len: int = 25,
                  a_len: int = 4, lr: float = 1e-4, tokenizer_vocab=None, train_lm_head: bool = False,
-                 dataset_resize: bool = True, **dims):
-        """dataset_resize: image LISTS pass the image datasets' Resize(384, max_size=640) first (cocoimages_dataset_crossvqas.py:83,
+                 dataset_resize: bool = True, optimizer_mode: str = "dat", **dims):
+        """optimizer_mode: "dat" (three adapters per module, AlbefDatEngine) or "adapter" (the FedAvg baseline: one adapter per
+        module, AlbefAdapterEngine; params from albef_spec / weights with the same optimizer_mode).  With "adapter" every key
+        containing 'adapter' is communicated, set_active_adapter('adapter') is the only accepted name, activate_gating() raises
+        (the reference's single-adapter modules have no gate and no other adapter), forward(train=False) ranks in mode "adapter".
+        dataset_resize: image LISTS pass the image datasets' Resize(384, max_size=640) first (cocoimages_dataset_crossvqas.py:83,
         108-109: every ALBEF image does); False for images that already went through it.
         train_lm_head: the LM head text_decoder.cls.predictions.* trains and is personal, as in the reference (main.py:127-128,
         247-250; AlbefDatEngine); state_dict() then carries its five tensors (not the tied aliases decoder.weight / decoder.bias).
@@ -41,14 +48,27 @@ class ALBEFContinualLearner:
         self.train_lm_head = bool(train_lm_head)
         self._vocab, self._tokenizer = tokenizer_vocab, None
         self.dataset_resize, self._image_transform = bool(dataset_resize), None
-        self.engine = AlbefDatEngine(params, self.device, batch=batch_size, n_answers=n_answers, q_len=q_len, a_len=a_len,
-                                     lr=lr, train_lm_head=self.train_lm_head, **dims)
+        if optimizer_mode not in ("dat", "adapter"):
+            raise L.FeddatHipError(f"ALBEF runs optimizer_mode 'dat' or 'adapter', got {optimizer_mode!r}")
+        self.optimizer_mode = optimizer_mode
+        engine_cls = AlbefDatEngine if optimizer_mode == "dat" else AlbefAdapterEngine
+        self.engine = engine_cls(params, self.device, batch=batch_size, n_answers=n_answers, q_len=q_len, a_len=a_len,
+                                 lr=lr, train_lm_head=self.train_lm_head, **dims)
+        if optimizer_mode == "adapter":
+            self.gating, self.active = False, "adapter"
+            self.adapter_requires_grad = {0: True}                                   # main.py:144-146
+            self.comm_state_dict_names = [n for n in self.state_dict() if "adapter" in n]      # main.py:147-149
+            return
         self.gating, self.active = False, "adapter_1"
         # prepare_model's initial state (main.py:157-159 + adapter.py:55-58): adapter_0/1 trainable, adapter_2 frozen
         self.adapter_requires_grad = {0: True, 1: True, 2: False}
         self.comm_state_dict_names = [n for n in self.state_dict() if "adapter_1" in n]   # main.py:160-163
 
     def set_active_adapter(self, name):          # albef.py:139-147 -> adapter.py:60-85 (requires_grad toggling included)
+        if self.optimizer_mode == "adapter":
+            if name != "adapter":
+                raise L.FeddatHipError(f"a single-adapter ALBEF has the adapter 'adapter' only, got {name!r}")
+            return
         self.active = name
         if name == "adapter_0":
             self.adapter_requires_grad[0], self.adapter_requires_grad[1] = True, False
@@ -56,13 +76,15 @@ class ALBEFContinualLearner:
             self.adapter_requires_grad[1], self.adapter_requires_grad[0] = True, False
 
     def activate_gating(self):                   # albef.py:161-169
+        if self.optimizer_mode == "adapter":
+            raise L.FeddatHipError("a single-adapter ALBEF has no gate (activate_gating is a dat call)")
         self.gating = True
 
     def deactivate_gating(self):                 # albef.py:150-158
         self.gating = False
 
     def optimizer_adapters(self) -> Sequence[int]:
-        return tuple(a for a in (0, 1) if self.adapter_requires_grad[a])
+        return tuple(a for a in (0, 1) if self.adapter_requires_grad.get(a, False))
 
     def state_dict(self) -> Dict[str, torch.Tensor]:
         return self.engine.state_dict()
@@ -182,12 +204,13 @@ class ALBEFContinualLearner:
 
 def create_albef_continual_learner_model(params: Dict[str, torch.Tensor], device, batch_size: int, n_answers: int,
                                          q_len: int = 25, a_len: int = 4, lr: float = 1e-4, tokenizer_vocab=None,
-                                         train_lm_head: bool = False, dataset_resize: bool = True,
+                                         train_lm_head: bool = False, dataset_resize: bool = True, optimizer_mode: str = "dat",
                                          **dims) -> ALBEFContinualLearner:
     """albef.py:255-273 (the ALBEF.pth checkpoint is passed in as a tensor dict: feddat_amd.weights.load_albef_pretrained
     reads it from a local file; there is no hub access here)."""
     return ALBEFContinualLearner(params, device, batch_size, n_answers, q_len, a_len, lr, tokenizer_vocab=tokenizer_vocab,
-                                 train_lm_head=train_lm_head, dataset_resize=dataset_resize, **dims)
+                                 train_lm_head=train_lm_head, dataset_resize=dataset_resize, optimizer_mode=optimizer_mode,
+                                 **dims)
 
 
 def convert_batch_to_albef_input_dict(batch):

@@ -48,9 +48,10 @@ class AlbefRank:
 
     @contextlib.contextmanager
     def _as_mode(self, mode: str):
-        """A forward in adapter mode `mode` ('gating' | 'adapter_k') runs in the buffers of an activation set the engine has:
-        that set, registered under `mode` for the length of the block."""
-        key = "gating" if mode == "gating" else "adapter_1"
+        """A forward in adapter mode `mode` ('gating' | 'adapter_k'; 'adapter' on a single-adapter engine) runs in the buffers of
+        an activation set the engine has (the backbone's ACT_SETS: the mode's own, else the last): that set, registered under
+        `mode` for the length of the block."""
+        key = mode if mode in self.ACT_SETS else self.ACT_SETS[-1]
         S = self.acts[key]
         self.acts[mode] = S
         try:

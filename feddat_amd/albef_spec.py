@@ -10,20 +10,28 @@ from typing import Dict, Sequence, Tuple
 import torch
 
 PRE = "albef_model.albef."
+# the adapters every module carries, per optimizer_mode: what follows "<module>.adapter." in a key, up to "down" / "up"
+ADAPTER_STEMS = {"dat": ("adapter_0_", "adapter_1_", "adapter_2_"), "adapter": ("adapter_",)}
 
 
 def param_shapes(vit_depth: int = 12, enc_layers: int = 12, fusion_layer: int = 6, dec_layers: int = 6, image: int = 384,
                  patch: int = 16, hidden: int = 768, inter: int = 3072, vocab: int = 30522, max_pos: int = 512,
-                 bottleneck: int = 48) -> Dict[str, Tuple[int, ...]]:
+                 bottleneck: int = 48, optimizer_mode: str = "dat") -> Dict[str, Tuple[int, ...]]:
+    """optimizer_mode "dat": three adapters per module (adapter_{0,1,2}_{down,up}); "adapter": the single-adapter FedAvg build
+    (adapter_config names = ["adapter"], main.py:114-118), one adapter_down / adapter_up pair per module.  Backbone and LM head
+    are the same."""
+    if optimizer_mode not in ("dat", "adapter"):
+        raise ValueError(f"ALBEF is built for optimizer_mode 'dat' or 'adapter', got {optimizer_mode!r}")
     H, I, r = hidden, inter, bottleneck
     s: Dict[str, Tuple[int, ...]] = {}
+    stems = ADAPTER_STEMS[optimizer_mode]
 
     def adapters(base):
-        for a in range(3):
-            s[f"{base}adapter_{a}_down.weight"] = (r, H)
-            s[f"{base}adapter_{a}_down.bias"] = (r,)
-            s[f"{base}adapter_{a}_up.weight"] = (H, r)
-            s[f"{base}adapter_{a}_up.bias"] = (H,)
+        for stem in stems:
+            s[f"{base}{stem}down.weight"] = (r, H)
+            s[f"{base}{stem}down.bias"] = (r,)
+            s[f"{base}{stem}up.weight"] = (H, r)
+            s[f"{base}{stem}up.bias"] = (H,)
 
     v = PRE + "visual_encoder."
     s[v + "cls_token"] = (1, 1, H)

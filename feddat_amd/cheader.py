@@ -1,11 +1,12 @@
-"""Reader of the C ABI headers (include/feddat_hip.h, include/feddat_hip_prompt.h): what feddat_amd/lib.py binds with ctypes.
+"""Reader of the C ABI headers (include/feddat_hip.h and its extension headers include/feddat_hip_prompt.h and
+include/feddat_hip_albef.h): what feddat_amd/lib.py binds with ctypes.
 
-Not a C parser: it reads the constructs these two headers contain -- block comments, preprocessor lines, `typedef struct`
+Not a C parser: it reads the constructs these headers contain -- block comments, preprocessor lines, `typedef struct`
 (complete or opaque), int / long functions named feddat_* -- and raises HeaderError on anything else, at import: a type it
 does not know, a declaration it cannot read or any text left over stops the binding instead of being bound by a guess.
 Pure Python (no torch, nothing from the package), so it is tested without the library.
 
-MAIN / PROMPT, one Header per file:
+MAIN / PROMPT / ALBEF, one Header per file:
   functions  name -> (restype, [(ctype, parameter name), ...])                in declaration order
   structs    typedef name -> [(field name, ctype), ...]                       scalars, pointers and fixed arrays
   types      typedef name -> the ctypes.Structure class with those _fields_
@@ -91,3 +92,4 @@ class Header:
 
 MAIN = Header("feddat_hip.h")
 PROMPT = Header("feddat_hip_prompt.h", MAIN)
+ALBEF = Header("feddat_hip_albef.h", MAIN)

@@ -1,6 +1,7 @@
 // Small kernels of the ALBEF path (configs[3]): the LM-head token loss with vocabulary-axis MKD, row gather / segment sum
 // (answers <-> questions), and a 3-operand element-wise combine used around the BERT double-LayerNorm adapter variant.
 #include "common.hip.h"
+#include "../../include/feddat_hip_albef.h"
 
 namespace {
 
@@ -88,6 +89,9 @@ __device__ __forceinline__ float block_sum(float v, float* red) {
 // 1024 threads per row, 16-byte loads (rows are 16-byte aligned: ldl % 4 == 0 is checked by the launcher): with 256 threads
 // and scalar loads the three passes over 30 522 columns were 360 dependent load -> exp iterations per thread (206 us for
 // the 96 rows of the bench configuration, on the critical path between the forward and the backward pass).
+// CE_ONLY (feddat_lm_ce_loss_fwd_bwd, the single-adapter FedAvg step): the same kernel without a teacher at COMPILE time -- no
+// teacher loads or tests in the three loops, no MKD term, factor 1 instead of 1/2: L = sum_r w_r ce_r.  Its dlogits are the bits
+// of the general form called with teacher = NULL and twice the grad_scale ((0.5f * 2 s) g and s g are the same float product).
 constexpr int LM_NT = 1024;
 __device__ __forceinline__ float block_max16(float v, float* red) {
     v = wave_max(v);
@@ -109,6 +113,7 @@ __device__ __forceinline__ float block_sum16(float v, float* red) {
     __syncthreads();
     return r;
 }
+template <bool CE_ONLY>
 __global__ __launch_bounds__(LM_NT) void lm_loss_kernel(const float* __restrict__ logits, const float* __restrict__ teacher,
                                                         long ldl, const long* __restrict__ labels,
                                                         const float* __restrict__ row_w, const float* __restrict__ row_kl,
@@ -119,7 +124,7 @@ __global__ __launch_bounds__(LM_NT) void lm_loss_kernel(const float* __restrict_
     if (grad_scale_dev) grad_scale *= *grad_scale_dev;      // the dynamic loss scale (a power of two: exact)
     const int r = blockIdx.x, tid = threadIdx.x;
     const float* l = logits + (size_t)r * ldl;
-    const float* t = teacher ? teacher + (size_t)r * ldl : nullptr;
+    const float* t = (!CE_ONLY && teacher) ? teacher + (size_t)r * ldl : nullptr;
     const float invT = 1.0f / T;
     const int V4 = V & ~3;                      // whole 4-column groups; columns [V4, V) go to threads 0 .. V - V4 - 1
     const int vt = V4 + tid;                    // this thread's tail column (if < V)
@@ -183,7 +188,8 @@ __global__ __launch_bounds__(LM_NT) void lm_loss_kernel(const float* __restrict_
         const float d = lv - m1;
         float gv = w * (__expf(d) * i1 - (v == lab ? 1.f : 0.f));
         if (t) gv += ks * (__expf(d * invT) * ip - __expf((tv - mt) * invT) * iq);
-        return (0.5f * grad_scale) * gv;      // grad_scale: the caller's power-of-two loss scale (fp16 operand build), else 1
+        // grad_scale: the caller's power-of-two loss scale (fp16 operand build), else 1
+        return (CE_ONLY ? grad_scale : 0.5f * grad_scale) * gv;
     };
     for (int v = 4 * tid; v < V4; v += 4 * LM_NT) {          // (ldd % 4 == 0 and dlogits 8-byte aligned: launcher)
         const f32x4 lv = *reinterpret_cast<const f32x4*>(l + v);
@@ -199,6 +205,8 @@ __global__ __launch_bounds__(LM_NT) void lm_loss_kernel(const float* __restrict_
 }
 
 // scalars[0] = sum_r w_r ce_r (the loss ALBEF.forward returns), [1] = kl_scale * sum_r kl_r, [2] = ([0] + [1]) / 2
+// CE_ONLY: [0] = [2] = the loss, [1] = 0.
+template <bool CE_ONLY>
 __global__ void lm_loss_finish(const float* __restrict__ row_terms, int R, float kl_scale, float* __restrict__ scalars,
                                int* __restrict__ nonfinite) {
     float ce = 0.f, kl = 0.f;
@@ -208,6 +216,15 @@ __global__ void lm_loss_finish(const float* __restrict__ row_terms, int R, float
     }
     ce = wave_sum(ce);
     kl = wave_sum(kl);
+    if (CE_ONLY) {
+        if (threadIdx.x == 0) {
+            scalars[0] = ce;
+            scalars[1] = 0.f;
+            scalars[2] = ce;
+            if (nonfinite && fd_nonfinite(ce)) atomicOr(nonfinite, 1);
+        }
+        return;
+    }
     if (threadIdx.x == 0) {
         scalars[0] = ce;
         scalars[1] = kl * kl_scale;
@@ -537,9 +554,9 @@ extern "C" int feddat_lm_loss_fwd_bwd(const float* logits, const float* teacher,
     float* row_terms = scalars + 4;       // scalars: 4 + 2 R floats
     FD_CHECK_ARG(ldl % 4 == 0 && ((uintptr_t)logits & 15) == 0 && (!teacher || ((uintptr_t)teacher & 15) == 0));
     FD_CHECK_ARG(!dlogits_bf16 || (ldd % 4 == 0 && ((uintptr_t)dlogits_bf16 & 7) == 0));
-    hipLaunchKernelGGL(lm_loss_kernel, dim3(R), dim3(LM_NT), 0, stream, logits, teacher, ldl, labels, row_weight, row_kl, V, temp,
+    hipLaunchKernelGGL(lm_loss_kernel<false>, dim3(R), dim3(LM_NT), 0, stream, logits, teacher, ldl, labels, row_weight, row_kl, V, temp,
                        kl_scale, (bf16*)dlogits_bf16, ldd, row_terms, grad_scale, (const float*)nullptr);
-    hipLaunchKernelGGL(lm_loss_finish, dim3(1), dim3(64), 0, stream, row_terms, R, kl_scale, scalars, (int*)nullptr);
+    hipLaunchKernelGGL(lm_loss_finish<false>, dim3(1), dim3(64), 0, stream, row_terms, R, kl_scale, scalars, (int*)nullptr);
     FD_LAUNCH_RET();
 }
 
@@ -552,8 +569,23 @@ extern "C" int feddat_lm_loss_fwd_bwd_dyn(const float* logits, const float* teac
     float* row_terms = scalars + 4;       // scalars: 4 + 2 R floats
     FD_CHECK_ARG(ldl % 4 == 0 && ((uintptr_t)logits & 15) == 0 && (!teacher || ((uintptr_t)teacher & 15) == 0));
     FD_CHECK_ARG(!dlogits_bf16 || (ldd % 4 == 0 && ((uintptr_t)dlogits_bf16 & 7) == 0));
-    hipLaunchKernelGGL(lm_loss_kernel, dim3(R), dim3(LM_NT), 0, stream, logits, teacher, ldl, labels, row_weight, row_kl, V, temp,
+    hipLaunchKernelGGL(lm_loss_kernel<false>, dim3(R), dim3(LM_NT), 0, stream, logits, teacher, ldl, labels, row_weight, row_kl, V, temp,
                        kl_scale, (bf16*)dlogits_bf16, ldd, row_terms, grad_scale, grad_scale_dev);
-    hipLaunchKernelGGL(lm_loss_finish, dim3(1), dim3(64), 0, stream, row_terms, R, kl_scale, scalars, nonfinite);
+    hipLaunchKernelGGL(lm_loss_finish<false>, dim3(1), dim3(64), 0, stream, row_terms, R, kl_scale, scalars, nonfinite);
+    FD_LAUNCH_RET();
+}
+
+// The LM loss without a teacher (include/feddat_hip_albef.h): L = sum_r row_weight[r] ce_r, the CE_ONLY instantiation.
+extern "C" int feddat_lm_ce_loss_fwd_bwd(const float* logits, long ldl, const long* labels, const float* row_weight, int R, int V,
+                                         float grad_scale, const float* grad_scale_dev, int* nonfinite, void* dlogits_bf16,
+                                         long ldd, float* scalars, hipStream_t stream) {
+    FD_CHECK_ARG(logits && labels && row_weight && scalars && R > 0 && V > 0 && ldl >= V && grad_scale > 0.f);
+    FD_CHECK_ARG(!dlogits_bf16 || ldd >= V);
+    float* row_terms = scalars + 4;       // scalars: 4 + 2 R floats
+    FD_CHECK_ARG(ldl % 4 == 0 && ((uintptr_t)logits & 15) == 0);
+    FD_CHECK_ARG(!dlogits_bf16 || (ldd % 4 == 0 && ((uintptr_t)dlogits_bf16 & 7) == 0));
+    hipLaunchKernelGGL(lm_loss_kernel<true>, dim3(R), dim3(LM_NT), 0, stream, logits, (const float*)nullptr, ldl, labels, row_weight,
+                       (const float*)nullptr, V, 1.0f, 0.0f, (bf16*)dlogits_bf16, ldd, row_terms, grad_scale, grad_scale_dev);
+    hipLaunchKernelGGL(lm_loss_finish<true>, dim3(1), dim3(64), 0, stream, row_terms, R, 0.0f, scalars, nonfinite);
     FD_LAUNCH_RET();
 }

@@ -1,4 +1,5 @@
-"""ctypes binding of libfeddat_hip.so (include/feddat_hip.h and its extension header include/feddat_hip_prompt.h).
+"""ctypes binding of libfeddat_hip.so (include/feddat_hip.h and its extension headers include/feddat_hip_prompt.h and
+include/feddat_hip_albef.h).
 
 The HIP library is THE product path: if it cannot be loaded this module raises -- there is no eager /
 PyTorch / CPU fallback anywhere in feddat_amd.  torch is used only as plumbing: device allocations
@@ -70,6 +71,10 @@ EXPORTED_SYMBOLS = tuple(_SIGS)
 # the extension header include/feddat_hip_prompt.h (csrc/prompt.hip): the same libraries
 _PROMPT_SIGS = {name: [t for t, _ in params] for name, (_, params) in _H.PROMPT.functions.items()}
 PROMPT_SYMBOLS = tuple(_PROMPT_SIGS)
+# the extension header include/feddat_hip_albef.h (csrc/albef_misc.hip): the same libraries.  Its functions are called by name
+# through _ext (below), not as attributes of the loaded library
+_ALBEF_SIGS = {name: [t for t, _ in params] for name, (_, params) in _H.ALBEF.functions.items()}
+ALBEF_SYMBOLS = tuple(_ALBEF_SIGS)
 
 
 class FeddatHipError(RuntimeError):
@@ -87,7 +92,7 @@ def _open(path: str, want_format: int) -> C.CDLL:
             f"{path} not found: the HIP library is the only implementation of this path "
             "(no CPU/PyTorch fallback). Build it with `python __graft_entry__.py` or `python -m feddat_amd.build`.")
     lib = C.CDLL(path)
-    for header, sigs in ((_H.MAIN, _SIGS), (_H.PROMPT, _PROMPT_SIGS)):
+    for header, sigs in ((_H.MAIN, _SIGS), (_H.PROMPT, _PROMPT_SIGS), (_H.ALBEF, _ALBEF_SIGS)):
         for name, args in sigs.items():
             fn = getattr(lib, name)
             fn.argtypes, fn.restype = args, header.functions[name][0]
@@ -251,6 +256,13 @@ def _stream():
 def _chk(rc: int, what: str):
     if rc != 0:
         raise FeddatHipError(f"{what} failed with code {rc} ({ {1: 'EINVAL', 2: 'ELAUNCH', 3: 'ETIMEOUT'}.get(rc, '?') })")
+
+
+def _ext(name: str):
+    """The bound function `name` of the extension header include/feddat_hip_albef.h, from the calling thread's library."""
+    if name not in _ALBEF_SIGS:
+        raise FeddatHipError(f"{name} is not declared in include/feddat_hip_albef.h")
+    return getattr(load(), name)
 
 
 def _dev(*ts):
@@ -901,6 +913,19 @@ def lm_loss_fwd_bwd(logits, teacher, labels, row_weight, V, temp, kl_scale, dlog
     _chk(load().feddat_lm_loss_fwd_bwd(_p(logits), _p(teacher), logits.stride(0), _p(labels), _p(row_weight), _p(row_kl), R, V, temp,
                                        kl_scale, float(grad_scale), _p(dlogits_bf16), 0 if dlogits_bf16 is None else dlogits_bf16.stride(0),
                                        _p(scalars), _stream()), "feddat_lm_loss_fwd_bwd")
+
+
+def lm_ce_loss_fwd_bwd(logits, labels, row_weight, V, dlogits_bf16, scalars, grad_scale=1.0, grad_scale_dev=None, nonfinite=None):
+    """L = sum_r row_weight[r] ce_r, the LM loss without a teacher (include/feddat_hip_albef.h): scalars[0] = scalars[2] = L,
+    dlogits = grad_scale * (*grad_scale_dev) * dL/dlogits in the operand format."""
+    _dev(logits, labels, row_weight, dlogits_bf16, scalars, grad_scale_dev, nonfinite)
+    R = logits.shape[0]
+    assert scalars.numel() >= 4 + 2 * R and labels.dtype == torch.int64 and labels.numel() >= R and row_weight.numel() >= R
+    assert dlogits_bf16 is None or dlogits_bf16.shape[0] >= R
+    _chk(_ext("feddat_lm_ce_loss_fwd_bwd")(_p(logits), logits.stride(0), _p(labels), _p(row_weight), R, V, float(grad_scale),
+                                           _p(grad_scale_dev), _p(nonfinite), _p(dlogits_bf16),
+                                           0 if dlogits_bf16 is None else dlogits_bf16.stride(0), _p(scalars), _stream()),
+         "feddat_lm_ce_loss_fwd_bwd")
 
 
 def vilt_stage_inputs(input_ids, token_type_ids, attention_mask, target, pixel_mask, dst: dict, B, Lt, n_labels, Hi, Wi, P):

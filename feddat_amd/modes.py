@@ -7,7 +7,7 @@ module does the same on the keys it is given.
   dat        adapter_0, adapter_1, heads    adapter_1                 heads, adapter_0, adapter_2
              (heads: ViLT's task_layer.* ('task'); ALBEF's text_decoder.cls.predictions.* ('.cls.'), present in an ALBEF state dict
              only when the model was built with train_lm_head=True)
-  adapter    adapter, heads                 every 'adapter' key       heads ('task')
+  adapter    adapter, heads                 every 'adapter' key       heads ('task'; albef=True: '.cls.' too)
   bias       every 'bias' key, heads        every 'bias' key          heads ('task')
   norm       every 'norm' key, heads        every 'norm' key          heads ('task')
   prompt     every 'prompt' key, heads      every 'prompt' key        heads ('task')
@@ -52,8 +52,10 @@ ADAPTERLESS_MODES = VECTOR_MODES + (PROMPT_MODE,)
 SINGLE_PASS_MODES = ("adapter",) + ADAPTERLESS_MODES
 
 
-def mode_names(keys: Sequence[str], mode: str) -> Dict[str, List[str]]:
-    """{"trainable", "communicated", "personal"}: the subsets of `keys` (state-dict order kept) for optimizer_mode `mode`."""
+def mode_names(keys: Sequence[str], mode: str, albef: bool = False) -> Dict[str, List[str]]:
+    """{"trainable", "communicated", "personal"}: the subsets of `keys` (state-dict order kept) for optimizer_mode `mode`.
+    albef: the keys are an ALBEF model's (encoder_name albef*): in the non-dat modes its LM head ('.cls.') trains and is personal
+    too, as main.py:127-128,247-250 has it; dat treats '.cls.' that way on any key list."""
     if mode not in MODES + (PROMPT_MODE,):
         raise L.FeddatHipError(f"optimizer_mode must be one of {MODES + (PROMPT_MODE,)}, got {mode!r}")
     keys = list(keys)
@@ -63,9 +65,12 @@ def mode_names(keys: Sequence[str], mode: str) -> Dict[str, List[str]]:
                     communicated=[k for k in keys if "adapter_1" in k],
                     personal=[k for k in keys if "task" in k or ".cls." in k or "adapter_0" in k or "adapter_2" in k])
     sub = mode          # "adapter" | "bias" | "norm" | "prompt": the substring main.py matches is the mode's own name
-    return dict(trainable=[k for k in keys if sub in k or "task" in k],
+    # the heads: 'task' (ViLT); with albef=True '.cls.' as well, the decoder's LM head, trainable and personal where the encoder
+    # is ALBEF (main.py:127-128,247-250)
+    head = (lambda k: "task" in k or ".cls." in k) if albef else (lambda k: "task" in k)
+    return dict(trainable=[k for k in keys if sub in k or head(k)],
                 communicated=[k for k in keys if sub in k],
-                personal=[k for k in keys if "task" in k])
+                personal=[k for k in keys if head(k)])
 
 
 def averaged_names(keys: Sequence[str], mode: str) -> List[str]:

@@ -201,7 +201,8 @@ class TaskTrainer:
 
 class AlbefTaskTrainer(TaskTrainer):
     """The same trainer driving the ALBEF model (encoder_name albef_no_distill: task_trainer.py:250-264,296-297,316-317;
-    eval with answer ranking :159-204).  Batches are the tokenised dicts of feddat_amd.albef_spec.synthetic_batch."""
+    eval with answer ranking :159-204).  The mode is the model's (ALBEFContinualLearner.optimizer_mode): with "adapter" a step
+    is the non-dat one and eval returns one score (task_trainer.py:232-246).  Batches are the tokenised dicts of feddat_amd.albef_spec.synthetic_batch."""
 
     def train(self, model, *unused):
         eng = model.engine
@@ -210,7 +211,8 @@ class AlbefTaskTrainer(TaskTrainer):
         eng.begin_local_update(steps_per_epoch=len(self.vqa_train_dataloader), num_epochs=self.num_epochs,
                                warmup_ratio=self.warmup_ratio, opt_adapters=optimizer.adapters,
                                dropout_epoch=getattr(self, "dropout_epoch", 0))
-        model.adapter_requires_grad[2] = False
+        if self._mode(model) == "dat":
+            model.adapter_requires_grad[2] = False
         for epoch in range(self.local_epochs):
             for step, batch in enumerate(self.vqa_train_dataloader):
                 if self.args.debug > 0 and step > self.args.debug:
@@ -227,6 +229,8 @@ class AlbefTaskTrainer(TaskTrainer):
         if "questions" in batch or model.image_list(batch) is not None:
             batch = model.process_inputs(dict(batch, train=True))
         out = model.engine.train_step(batch, use_graph=self.use_graph)
+        if self._mode(model) in SINGLE_PASS_MODES:      # task_trainer.py:433-450: no gate to leave on
+            return out[0]
         model.activate_gating()
         model.set_active_adapter("adapter_0")
         return out[0]

@@ -255,9 +255,10 @@ def convert_albef_state_dict(sd: Dict[str, torch.Tensor], image: int = 384, patc
     return out
 
 
-def load_albef_pretrained(path: str, seed: int = 0, image: int = 384, **dims) -> Dict[str, torch.Tensor]:
+def load_albef_pretrained(path: str, seed: int = 0, image: int = 384, optimizer_mode: str = "dat", **dims) -> Dict[str, torch.Tensor]:
+    """optimizer_mode "dat" | "adapter": which adapters are created beside the checkpoint's tensors (albef_spec.param_shapes)."""
     sd = convert_albef_state_dict(read_checkpoint(path), image=image, **dims)
-    shapes = albef_spec.param_shapes(image=image, **dims)
+    shapes = albef_spec.param_shapes(image=image, optimizer_mode=optimizer_mode, **dims)
     sd.update(init_trainable({k: v for k, v in shapes.items() if k not in sd}, seed))
     lack = [k for k in shapes if k not in sd]             # every expected key has a source (as in load_vilt_pretrained)
     if lack:

@@ -4,13 +4,14 @@ settings: every group the step updates (_named_groups(), in that order: adapter_
 with the same hash run the same arithmetic: at 80 steps the AdamW trajectory is chaotic enough that a last-bit change moves the
 round-length parity draws ("draws"), so a change meant to be arithmetic-neutral -- a kernel, or the host
 sequencing of an engine -- is checked with this before the 80-step tests are trusted.
-python tools/state_hash.py [repo root] [--engine dat | dat-fp8 | adapter | bias | norm | prompt | albef | albef-head | albef-dropout | albef-stack] [--layers N]
-(albef: the full-size AlbefDatEngine at B = 4, default settings -- the LM head frozen --, 12 replayed steps; albef-head: train_lm_head=True, albef-dropout: dropout=0.1, albef-stack: stack_text=True, each otherwise the same; the albef lines end with torch.cuda.max_memory_allocated() after the engine's construction; the repo root is the tree whose feddat_amd is hashed, so one copy of this tool compares two trees)
+python tools/state_hash.py [repo root] [--engine dat | dat-fp8 | adapter | bias | norm | prompt | albef | albef-head | albef-dropout | albef-stack | albef_adapter | albef_adapter-head] [--layers N]
+(albef: the full-size AlbefDatEngine at B = 4, default settings -- the LM head frozen --, 12 replayed steps; albef-head: train_lm_head=True, albef-dropout: dropout=0.1, albef-stack: stack_text=True, each otherwise the same; albef_adapter / albef_adapter-head: the single-adapter AlbefAdapterEngine, head frozen / trained, same protocol; the albef lines end with torch.cuda.max_memory_allocated() after the engine's construction; the repo root is the tree whose feddat_amd is hashed, so one copy of this tool compares two trees)
 dat, round 6 HEAD (= round 5's arithmetic): cb900273526616cd; the other engines: DESIGN.md sections 13, 14 and 21 (prompt, and --layers 1)"""
 import argparse, sys, os, hashlib, torch
 ap = argparse.ArgumentParser()
 ap.add_argument("root", nargs="?", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-ALBEF = {"albef": {}, "albef-head": dict(train_lm_head=True), "albef-dropout": dict(dropout=0.1), "albef-stack": dict(stack_text=True)}
+ALBEF = {"albef": {}, "albef-head": dict(train_lm_head=True), "albef-dropout": dict(dropout=0.1), "albef-stack": dict(stack_text=True),
+         "albef_adapter": {}, "albef_adapter-head": dict(train_lm_head=True)}
 ap.add_argument("--engine", choices=("dat", "dat-fp8", "adapter", "bias", "norm", "prompt") + tuple(ALBEF), default="dat")
 ap.add_argument("--layers", type=int, default=12, help="encoder layers of the ViLT engines (1: the top layer is layer 0)")
 args = ap.parse_args()
@@ -20,8 +21,13 @@ from feddat_amd import engine, vilt_spec
 dev = torch.device("cuda", 0)
 if args.engine in ALBEF:
     from feddat_amd import albef_engine, albef_spec
-    e = albef_engine.AlbefDatEngine(albef_spec.random_init(seed=0, image=384), dev, batch=4, n_answers=4, image=384,
-                                    **ALBEF[args.engine])
+    if args.engine.startswith("albef_adapter"):
+        from feddat_amd.albef_adapter_engine import AlbefAdapterEngine
+        e = AlbefAdapterEngine(albef_spec.random_init(seed=0, image=384, optimizer_mode="adapter"), dev, batch=4, n_answers=4,
+                               image=384, **ALBEF[args.engine])
+    else:
+        e = albef_engine.AlbefDatEngine(albef_spec.random_init(seed=0, image=384), dev, batch=4, n_answers=4, image=384,
+                                        **ALBEF[args.engine])
     mem = torch.cuda.max_memory_allocated()
     batches = [albef_spec.synthetic_batch(4, 1234 + i, image=384, device=dev) for i in range(4)]
     e.begin_local_update(steps_per_epoch=80)
